@@ -8,6 +8,13 @@ variational lower bound (one host sync).  x is resident in HBM before the timed 
 ``value`` = rows processed by all ranks per second.
 
     python bench.py --gpus N --steps K --warmup W [--config c3|c4|c2] [--scaling weak|strong] [--overlap] [--dense]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if ``--dump-outputs`` is given
+(dump_outputs: the same seeded inputs every run, so two builds can be compared output for output) and prints the line: the
+contract's keys (``ms_per_step`` = milliseconds per timed step), ``config``, ``window``, ``first_step_ms`` / ``last_step_ms``.
+Everything else below - HIP events inside the timed steps and the roofline built from them, cpu_baseline and parity, the
+legs and sub-lines, the ``--detail`` record - runs with ``--full`` only.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself (before this
 process touches a GPU); under ``python -m torch.distributed.run`` the ranks come from the environment.  Every rank
@@ -18,11 +25,11 @@ Configurations (BASELINE.json ``configs``): c3 = K64 D128 N1e7 f32 (default, the
 c4 = K256 D64 1.25e7 rows per GPU (N = 1e8 over 8 GPUs), c2 = K16 D32 N1e6 f64.  ``--scaling weak`` (default):
 every rank holds the configuration's rows; ``--scaling strong``: ``--total-rows`` are split over the ranks.
 
-Output: stdout carries ONE compact JSON line (< 6 KB: the contract's keys, `roofline`, `cpu_baseline`, both parity legs,
-`window`, `full_fit_seconds`, `dense_floor_samples_per_s`, the sub-lines `hmm_c5`, `c2`, `c4_shard`, `c4_strong`); the full
-record with every leg, per-step lists and kernel groups goes to ``--detail`` (default gpurun_out/bench_detail.json).
+Output: stdout carries ONE compact JSON line (< 6 KB; with ``--full`` also `roofline`, `cpu_baseline`, both parity legs,
+`full_fit_seconds`, `dense_floor_samples_per_s`, the sub-lines `hmm_c5`, `c2`, `c4_shard`, `c4_strong`); the full
+record with every leg, per-step lists and kernel groups goes to ``--detail`` (``--full``; its default is in parse_args).
 Default legs: dense, full, hmm, c2, c4, c4strong (about a minute); hard, spread, offpath, small on request (``--legs all``).
-With ``--gpus N`` > 1 the line carries the C3 weak-scaling window and, as `c4_strong`, config 4's N = 1e8 split over the N
+With ``--gpus N`` > 1 the line carries the C3 weak-scaling window and, with ``--full``, as `c4_strong`, config 4's N = 1e8 split over the N
 ranks (ms_per_step, per_rank_ms_per_step, allreduce_ms from its own HIP events, estep_kinds_identical_across_ranks); the
 one-GPU record carries the same job as resident row tiles - the strong-scaling curve is the ratio of those sub-lines.
 
@@ -120,7 +127,16 @@ def parse_args():
                          "watchdog dumps every thread's stack and exits non-zero (a stalled RCCL init must not hang the job)")
     ap.add_argument("--native-allreduce", action="store_true",
                     help="per-iteration all-reduce through the library's own RCCL communicator (gmmvb_allreduce_stats)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (HIP events inside the timed steps), cpu_baseline and parity, "
+                         "the legs and sub-lines, the --detail record.  Without it the run sets up, warms up, times the steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def visible_gpus():
@@ -353,8 +369,10 @@ class Workload:
         self.m = gm.LearnModel(K, D, seed=0, device=dev, comm=comm, verbose=False)
         self.eng, self.xd = self.m._open(x)
         # HIP events in the library (include/gmmvb.h: gmmvb_profile_enable): every record costs the stream ~10 us, so the
-        # timed steps of the headline keep only the spans of the groups that can dominate ("dominant", level 2)
-        self.eng.profile(2 if spans == "dominant" else 1)
+        # timed steps of the headline keep only the spans of the groups that can dominate ("dominant", level 2); spans=None
+        # records none (a run without --full)
+        if spans is not None:
+            self.eng.profile(2 if spans == "dominant" else 1)
         prior = self.m._prior_tensors(dev)
         self.ks = self.m._stepper(self.eng, prior, self.xd)
         q = self.m._init_subsampling(self.eng, self.xd, _kside.post_from_prior(prior), self.m._comm.global_rows)
@@ -391,6 +409,35 @@ class Workload:
     def close(self):
         self.eng.close()
         self.m._engine = None
+
+
+DUMP_BYTES = 60_000_000          # (64 MB with room for the .npy headers)
+
+
+def dump_outputs(dirname, w):
+    """What update_posterior hands its caller when the last timed step is its last iteration, as ``dirname/<name>.npy``
+    (float64): the posterior the last data pass ran under (hn_*), that pass's statistics (ns, x_bar_vecs, s_mats), the lower
+    bound (vl) and the responsibilities (r_vecs).  At most DUMP_BYTES in all: r_vecs is a fixed sample of whole row blocks
+    (drawn from SEED, in row order) and, should the [K, ...] arrays alone pass half the budget, they keep a fixed sample of
+    components (also from SEED, in order)."""
+    ks, q = w.ks, w.ks.q
+    arrays = {"hn_alpha_vec": q.alpha, "hn_m_vecs": q.m, "hn_kappas": q.kappa, "hn_nus": q.nu, "hn_w_mats": q.w,
+              "hn_w_mats_inv": q.w_inv, "ns": ks.ns, "x_bar_vecs": ks.x_bar, "s_mats": ks.s}
+    arrays = {k: v.detach().double().cpu().numpy() for k, v in arrays.items()}
+    rng = np.random.default_rng(SEED)
+    K, n = w.K, w.n
+    per_component = sum(a[0].nbytes for a in arrays.values())
+    if per_component * K > DUMP_BYTES // 2:
+        keep = np.sort(rng.choice(K, DUMP_BYTES // 2 // per_component, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    arrays["vl"] = np.array([w.terms["vl"]], dtype=np.float64)
+    rows = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // (K * 8)
+    block = min(1024, n, rows)
+    starts = np.sort(rng.choice(n // block, min(n // block, rows // block), replace=False)) * block
+    arrays["r_vecs"] = np.concatenate([w.eng.responsibilities(int(s), block).double().cpu().numpy() for s in starts])
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def kernel_name(info_part):
@@ -472,17 +519,18 @@ def main():
     x = device_rows(K, D, n_local, tdtype, dev, SEED + 1 + rank, spread, head=x_ref if rank == 0 else None)
 
     cpu_base = parity = parity_sparse = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    do_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu
+    if do_cpu:
         cpu_base, parity, parity_sparse = cpu_baseline_and_parity(K, D, x_ref, dev, sweep_threads=True)
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu
 
-    w = Workload(K, D, x, dev, comm, spans=args.spans)
+    w = Workload(K, D, x, dev, comm, spans=args.spans if args.full else None)
     eng = w.eng
     torch.cuda.synchronize()
-    warm = [dict(w.snapshot(), what="pass after the subsampling initialisation")]
+    warm = [dict(w.snapshot(), what="pass after the subsampling initialisation")] if args.full else []
     for _ in range(args.warmup):
         w.step()
-        warm.append(dict(w.snapshot(), what="warm-up iteration"))
+        if args.full:
+            warm.append(dict(w.snapshot(), what="warm-up iteration"))
 
     def fence():
         if use_dist:
@@ -490,7 +538,7 @@ def main():
         torch.cuda.synchronize()
 
     ker, launches, spars, spans, works = [], [], [], [], []
-    counts0 = eng.pass_counts()
+    counts0 = eng.pass_counts() if args.full else None
     # A full collection of Python's garbage collector inside the timed steps is a 40-70 ms host stall once
     # torch.distributed has been imported and initialised (measured: always the same step, profiles/r2_experiments.md):
     # collect now and move what is alive to the permanent generation.
@@ -503,21 +551,25 @@ def main():
         ts = time.perf_counter()
         vl = w.step()
         walls.append((time.perf_counter() - ts) * 1e3)
-        ker.append(eng.last_kernel_ms())        # events already complete: step() ended with a host sync
-        spans.append(eng.kernel_spans())
-        launches.append(eng.launch_info)
-        spars.append(eng.sparsity())
-        works.append(eng.work())
+        if args.full:
+            ker.append(eng.last_kernel_ms())        # events already complete: step() ended with a host sync
+            spans.append(eng.kernel_spans())
+            launches.append(eng.launch_info)
+            spars.append(eng.sparsity())
+            works.append(eng.work())
     fence()
     elapsed = time.perf_counter() - t0
-    counts1 = eng.pass_counts()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w)
+    counts1 = eng.pass_counts() if args.full else None
     policy_same = None
-    if use_dist:
+    if use_dist and args.full:
         # every rank's sequence of E-step kinds over the timed steps: one policy for all ranks (gmmvb_set_shard) means
         # they are identical
         seqs = [None] * world
         dist.all_gather_object(seqs, [kernel_name(l) for l in launches])
         policy_same = all(q == seqs[0] for q in seqs)
+    if use_dist:
         # every rank's own clock and step times, so that a straggler shows (value uses the max over ranks)
         ranks_info = [None] * world
         dist.all_gather_object(ranks_info, dict(rank=rank, elapsed_s=elapsed, ms_per_step=elapsed / args.steps * 1e3,
@@ -539,7 +591,7 @@ def main():
     if "all" in leg_names:
         leg_names = {"dense", "hard", "spread", "full", "hmm", "small", "offpath", "c2", "c4", "c4strong"}
     strong_leg = None
-    if world > 1 and "c4strong" in leg_names and not args.no_legs and not args.dense and args.config == "c3":
+    if args.full and world > 1 and "c4strong" in leg_names and not args.no_legs and not args.dense and args.config == "c3":
         tot4 = args.strong_total_rows
         n4 = tot4 // world + (1 if rank < tot4 % world else 0)
         strong_leg = config_subline("c4", dev, 5, 20, comm=comm, use_dist=True, rows=n4, seed=100 + rank, world=world)
@@ -553,11 +605,13 @@ def main():
     if rank == 0:
         steps = args.steps
         step_ms = elapsed / steps * 1e3
-        roof, groups, fl_pair, timed_counts = build_roofline(eng, K, D, dt, n_local, steps, args.warmup, step_ms, ker, spans,
-                                                             launches, spars, works, counts0, counts1, args.spans)
+        roof = None
+        if args.full:
+            roof, groups, fl_pair, timed_counts = build_roofline(eng, K, D, dt, n_local, steps, args.warmup, step_ms, ker, spans,
+                                                                 launches, spars, works, counts0, counts1, args.spans)
         last_launch = eng.launch_info
         dense_leg = hard = spread_leg = full_leg = hmm_leg = small_leg = offpath = c2_leg = c4_leg = None
-        if not args.dense and world == 1 and not args.no_legs:
+        if args.full and not args.dense and world == 1 and not args.no_legs:
             legs = leg_names
             if "dense" in legs:
                 dense_leg = dense_leg_run(w, K, D, n_local, fl_pair)
@@ -925,20 +979,21 @@ def compact_line(out):
     """The ONE line the driver parses (< 6 KB): the contract's keys + roofline + cpu_baseline + both parity legs + the
     scalars that say what was measured.  Everything else (per-step lists, kernel groups, legs in full) is in the
     detail record (--detail)."""
-    r = out["roofline"]
-    roof = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "frac_executed", "frac_on_F", "step_frac_on_F", "pruned",
-                     "traffic", "hbm_frac", "spans", "step_hbm_frac", "f64_mfma_ceiling_samples_per_s", "frac_note"))
-    roof["pairs_per_sample"] = {k: round(v, 4) for k, v in r["pairs_per_sample"].items()}
-    roof["kernel_groups_ms"] = {g: round(v["ms"], 4) for g, v in r["kernel_groups"].items()}
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data")}
     line["config"] = _pick(out["config"], ("workload", "classes", "degree", "rows_per_gpu", "rows_total", "x_storage",
                                            "cluster_spread", "parallelism", "row_tiles"))
     line["window"] = out["window"]
-    line["roofline"] = roof
-    line["cpu_baseline"] = _pick(out["cpu_baseline"], ("value", "unit", "cores", "kind", "sample", "threads_swept"))
-    for k in ("parity", "parity_sparse_path"):
-        line[k] = _pick(out[k], ("max_rel_err", "tolerance", "passed", "rows", "iterations", "path"))
+    r = out["roofline"]
+    if r is not None:        # (--full)
+        roof = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "frac_executed", "frac_on_F", "step_frac_on_F",
+                         "pruned", "traffic", "hbm_frac", "spans", "step_hbm_frac", "f64_mfma_ceiling_samples_per_s", "frac_note"))
+        roof["pairs_per_sample"] = {k: round(v, 4) for k, v in r["pairs_per_sample"].items()}
+        roof["kernel_groups_ms"] = {g: round(v["ms"], 4) for g, v in r["kernel_groups"].items()}
+        line["roofline"] = roof
+        line["cpu_baseline"] = _pick(out["cpu_baseline"], ("value", "unit", "cores", "kind", "sample", "threads_swept"))
+        for k in ("parity", "parity_sparse_path"):
+            line[k] = _pick(out[k], ("max_rel_err", "tolerance", "passed", "rows", "iterations", "path"))
     w = out["per_step"]["wall_ms"]
     line["first_step_ms"], line["last_step_ms"] = w[0], w[-1]
     if out.get("full_fit"):
@@ -976,13 +1031,14 @@ def compact_line(out):
 
 
 def emit(out, args):
-    """Full record to the detail file, the compact line - and nothing else - on stdout."""
+    """Full record to the detail file (--full), the compact line - and nothing else - on stdout."""
     line = compact_line(out)
-    if args.detail == "-":
+    detail = args.detail if args.full else ""
+    if detail == "-":
         show_stdout(True)
         print(json.dumps(out), flush=True)
         show_stdout(False)
-    elif args.detail:
+    elif detail:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
             with open(args.detail, "w") as f:

@@ -50,7 +50,7 @@ case $MODE in
         else
           envs=$v; [ "$v" = "-" ] && envs=""
         fi
-        env $envs timeout 900 python3 bench.py --no-cpu --no-legs --detail $OUT/${TAG}_ab_$i.json $ARGS > /dev/null 2> $OUT/${TAG}_ab_$i.err
+        env $envs timeout 900 python3 bench.py --full --no-cpu --no-legs --detail $OUT/${TAG}_ab_$i.json $ARGS > /dev/null 2> $OUT/${TAG}_ab_$i.err
         report_bench $OUT/${TAG}_ab_$i.json "$v"
       done
     done
@@ -60,7 +60,7 @@ case $MODE in
     i=0
     for v in "$@"; do
       i=$((i+1)); envs=$v; [ "$v" = "-" ] && envs=""
-      env $envs timeout 900 python3 bench.py --no-cpu --no-legs --detail $OUT/${TAG}_steps_$i.json $ARGS > /dev/null 2> $OUT/${TAG}_steps_$i.err
+      env $envs timeout 900 python3 bench.py --full --no-cpu --no-legs --detail $OUT/${TAG}_steps_$i.json $ARGS > /dev/null 2> $OUT/${TAG}_steps_$i.err
       python3 - $OUT/${TAG}_steps_$i.json "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); ps = d["per_step"]
@@ -109,7 +109,7 @@ PY
   trace)
     ARGS=$(bench_args "$1")
     rm -rf $ROOT/$OUT/${TAG}_trace
-    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/${TAG}_trace -- python3 $ROOT/bench.py --no-cpu --no-legs --detail $ROOT/$OUT/${TAG}_bench_detail_profiled.json $ARGS > $ROOT/$OUT/${TAG}_bench_line_profiled.json 2> $ROOT/$OUT/${TAG}_trace.err)
+    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/${TAG}_trace -- python3 $ROOT/bench.py --full --no-cpu --no-legs --detail $ROOT/$OUT/${TAG}_bench_detail_profiled.json $ARGS > $ROOT/$OUT/${TAG}_bench_line_profiled.json 2> $ROOT/$OUT/${TAG}_trace.err)
     python3 tools/summarize_rocprof.py $OUT/${TAG}_trace > $OUT/${TAG}_bench_kernel_summary.md 2>> $OUT/${TAG}_trace.err
     head -40 $OUT/${TAG}_bench_kernel_summary.md
     f=$(find $OUT/${TAG}_trace -name "*kernel_trace.csv" | head -1)
@@ -118,7 +118,7 @@ PY
   pmc)
     CTR=$(echo $1 | tr ',' ' '); ARGS=$(bench_args "$2")
     rm -rf $ROOT/$OUT/${TAG}_pmcx
-    (cd /tmp && timeout 900 rocprofv3 --pmc $CTR --output-format csv -d $ROOT/$OUT/${TAG}_pmcx -- python3 $ROOT/bench.py --no-cpu --no-legs --detail "" $ARGS > /dev/null 2> $ROOT/$OUT/${TAG}_pmcx.err)
+    (cd /tmp && timeout 900 rocprofv3 --pmc $CTR --output-format csv -d $ROOT/$OUT/${TAG}_pmcx -- python3 $ROOT/bench.py --full --no-cpu --no-legs --detail "" $ARGS > /dev/null 2> $ROOT/$OUT/${TAG}_pmcx.err)
     python3 - $OUT/${TAG}_pmcx <<'PY'
 import collections, csv, glob, sys
 rows = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -7,7 +7,7 @@ for rep in 1 2; do
   i=0
   for v in "$@"; do
     i=$((i+1)); envs=$v; [ "$v" = "-" ] && envs=""
-    env $envs timeout 900 python3 bench.py --no-cpu --legs full --steps 2 --warmup 1 --detail $OUT/${TAG}_fullfit_$i.json > /dev/null 2> $OUT/${TAG}_fullfit_$i.err
+    env $envs timeout 900 python3 bench.py --full --no-cpu --legs full --steps 2 --warmup 1 --detail $OUT/${TAG}_fullfit_$i.json > /dev/null 2> $OUT/${TAG}_fullfit_$i.err
     python3 - $OUT/${TAG}_fullfit_$i.json "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))["full_fit"]

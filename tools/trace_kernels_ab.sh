@@ -10,7 +10,7 @@ for v in "$@"; do
   unset BAYESML_AMD_LIB
   [ "$v" != "-" ] && export BAYESML_AMD_LIB=$ROOT/bayesml_amd/csrc/libgmmvb_$v.so
   rm -rf $ROOT/$OUT/${TAG}_kab_$v
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$OUT/${TAG}_kab_$v -- python3 $ROOT/bench.py --no-cpu --no-legs --detail "" $ARGS > /dev/null 2> $ROOT/$OUT/${TAG}_kab_$v.err)
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$OUT/${TAG}_kab_$v -- python3 $ROOT/bench.py --full --no-cpu --no-legs --detail "" $ARGS > /dev/null 2> $ROOT/$OUT/${TAG}_kab_$v.err)
   python3 - $OUT/${TAG}_kab_$v "$PAT" "$v" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
