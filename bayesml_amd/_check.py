@@ -123,3 +123,17 @@ def shape_consistency(val, val_name, correct, correct_name, exc):
     """_check.py:268-272."""
     if val != correct:
         raise exc(f"{val_name} must coincide with {correct_name}: {val_name} = {val}, {correct_name} = {correct}")
+
+
+def nonneg_int(val, name, exc):
+    """_check.py:34-38 — Python/NumPy integers >= 0 only."""
+    if _is_int(val) and val >= 0:
+        return val
+    raise exc(name + " must be int. Its value must be non-negative (including 0).")
+
+
+def float_in_closed01(val, name, exc):
+    """_check.py:10-17 — real scalar in [0, 1] (integers are cast to float)."""
+    if _is_real(val) and 0.0 <= val <= 1.0:
+        return float(val) if _is_int(val) else val
+    raise exc(name + " must be in [0,1].")
