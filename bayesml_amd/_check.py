@@ -9,6 +9,17 @@ import numpy as np
 _EPSILON = np.sqrt(np.finfo(np.float64).eps)
 
 
+# What each sample validator below says when it refuses (the one source of these messages): the scalar conjugate models check the TYPE of an array on the host
+# by these rules and leave the VALUE check to the data pass on the device (include/expfam.h: `bad`).
+SAMPLE_MSG = {
+    "nonneg_ints": " must be int or a numpy.ndarray whose dtype is int. Its values must be non-negative (including 0).",
+    "ints_of_01": " must be int or a numpy.ndarray whose dtype is int. Its values must be 0 or 1.",
+    "onehot_vecs": " must be a numpy.ndarray whose dtype is int and whose last axis constitutes one-hot vectors.",
+    "pos_floats": " must be float or a numpy.ndarray. Its values must be positive (not including 0)",
+    "floats": " must be float or a numpy.ndarray.",
+}
+
+
 def _is_int(v):
     return np.issubdtype(type(v), np.integer)
 
@@ -49,7 +60,7 @@ def floats(val, name, exc):
     kind = _arr_kind(val)
     if kind is not None:
         return val.astype(float) if kind == "i" else val
-    raise exc(name + " must be float or a numpy.ndarray.")
+    raise exc(name + SAMPLE_MSG["floats"])
 
 
 def pos_floats(val, name, exc):
@@ -59,7 +70,7 @@ def pos_floats(val, name, exc):
     kind = _arr_kind(val)
     if kind is not None and np.all(val > 0):
         return val.astype(float) if kind == "i" else val
-    raise exc(name + " must be float or a numpy.ndarray. Its values must be positive (not including 0)")
+    raise exc(name + SAMPLE_MSG["pos_floats"])
 
 
 def float_vec(val, name, exc):
@@ -137,3 +148,65 @@ def float_in_closed01(val, name, exc):
     if _is_real(val) and 0.0 <= val <= 1.0:
         return float(val) if _is_int(val) else val
     raise exc(name + " must be in [0,1].")
+
+
+def float_(val, name, exc):
+    """_check.py:156-161 — real scalar (integers are cast to float); no sign condition."""
+    if _is_real(val):
+        return float(val) if _is_int(val) else val
+    raise exc(name + " must be a scalar.")
+
+
+def nonneg_ints(val, name, exc):
+    """_check.py:40-48 — integer scalar >= 0, or integer ndarray whose values are all >= 0."""
+    if _is_int(val) and val >= 0:
+        return val
+    if _arr_kind(val) == "i" and np.all(val >= 0):
+        return val
+    raise exc(name + SAMPLE_MSG["nonneg_ints"])
+
+
+def int_of_01(val, name, exc):
+    """_check.py:91-95 — the integer 0 or 1 (bool and floats are rejected)."""
+    if _is_int(val) and (val == 0 or val == 1):
+        return val
+    raise exc(name + " must be int. Its value must be 0 or 1.")
+
+
+def ints_of_01(val, name, exc):
+    """_check.py:97-105 — the integer 0 or 1, or an integer ndarray of zeros and ones."""
+    if _is_int(val) and (val == 0 or val == 1):
+        return val
+    if _arr_kind(val) == "i" and np.all(val >= 0) and np.all(val <= 1):
+        return val
+    raise exc(name + SAMPLE_MSG["ints_of_01"])
+
+
+def onehot_vec(val, name, exc):
+    """_check.py:250-254 — 1-dimensional integer ndarray, no negative entry, entries summing to 1."""
+    if _arr_kind(val) == "i" and val.ndim == 1 and np.all(val >= 0) and val.sum() == 1:
+        return val
+    raise exc(name + " must be a one-hot vector (1-dimensional ndarray) whose dtype must be int.")
+
+
+def onehot_vecs(val, name, exc):
+    """_check.py:256-260 — integer ndarray (ndim >= 1), no negative entry, every last-axis sum equal to 1."""
+    if _arr_kind(val) == "i" and val.ndim >= 1 and np.all(val >= 0) and np.all(val.sum(axis=-1) == 1):
+        return val
+    raise exc(name + SAMPLE_MSG["onehot_vecs"])
+
+
+def sample_kind(val):
+    """'i' / 'f' for an integer / floating ndarray or torch tensor (bool, complex and everything else: None)."""
+    if type(val) is np.ndarray:
+        return _arr_kind(val)
+    try:
+        import torch
+    except ImportError:      # pragma: no cover
+        return None
+    if isinstance(val, torch.Tensor):
+        if val.dtype.is_floating_point:
+            return "f"
+        if val.dtype != torch.bool and not val.dtype.is_complex:
+            return "i"
+    return None

@@ -1,0 +1,5 @@
+"""Poisson model with a Gamma prior: drop-in for ``bayesml.poisson`` whose pass over an array sample runs on the
+MI355X (``csrc/expfam_kernels.h``)."""
+from ._poisson import GenModel, LearnModel
+
+__all__ = ["GenModel", "LearnModel"]
