@@ -1,0 +1,483 @@
+"""``contexttree.GenModel`` / ``LearnModel``: drop-in for ``bayesml/contexttree/_contexttree.py`` (cited below as
+``ref:<lines>``).
+
+The reference keeps the posterior as a tree of Python ``_Node`` objects and walks it once per symbol (ref:688-731).  Here
+the posterior lives in dense per-level tables on the device (``_ctree.CtreePass``) and ``update_posterior`` is the batch
+form of DESIGN.md "Context tree": ``ctree_count`` counts every (context, symbol) pair of the sample where it lies, one host
+read of ``[n | bad]`` decides whether the sample is accepted, and ``ctree_sweep`` applies the update level by level.
+``estimate_params`` runs ``ctree_map`` and builds only the pruned MAP tree.  What touches one root-to-leaf path
+(``calc_pred_dist``, ``pred_and_update``) gathers its D + 1 rows and works on the host.  ``hn_root`` is a property that
+materialises the ``_Node`` tree from the tables on demand; a tree given to a setter is scattered into them.
+
+``GenModel`` is host NumPy: the chain is sequential and short.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+from .. import _check, _ctree, base
+from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
+
+_INT_VEC_MSG = " must be a 1-dimensional numpy.ndarray whose dtype is int. Its values must be non-negative (including 0)."
+
+
+class _Node:
+    """ref:16-28, attribute for attribute."""
+
+    def __init__(self, depth, c_k, h_g=0.5):
+        self.depth = depth
+        self.children = [None for i in range(c_k)]  # child nodes
+        self.h_g = h_g
+        self.h_beta_vec = np.ones(c_k) / 2
+        self.theta_vec = np.ones(c_k) / c_k
+        self.leaf = False
+        self.map_leaf = False
+
+
+def _copy_h_tree(node, orig, c_k, c_d_max, g, beta_vec):
+    """The reference's ``_set_h_params_recursion`` family (ref:175-195, 504-533): superpose ``orig`` on ``node``; where
+    ``orig`` ends, the defaults ``g`` / ``beta_vec`` go to ``node`` and to everything below it."""
+    if orig is None:
+        node.h_g = 0.0 if node.depth == c_d_max else g
+        node.h_beta_vec[:] = beta_vec
+        for child in node.children:
+            if child is not None:
+                _copy_h_tree(child, None, c_k, c_d_max, g, beta_vec)
+        return
+    node.h_g = orig.h_g
+    node.h_beta_vec[:] = orig.h_beta_vec
+    if node.depth == c_d_max:
+        node.leaf = True
+        node.h_g = 0.0
+    elif orig.leaf:
+        node.leaf = True
+    else:
+        node.leaf = False
+        for i in range(c_k):
+            if node.children[i] is None:
+                node.children[i] = _Node(node.depth + 1, c_k)
+            _copy_h_tree(node.children[i], orig.children[i], c_k, c_d_max, g, beta_vec)
+
+
+def _fill_tree(node, c_d_max, g=None, beta_vec=None):
+    """ref:163-173: a new default for every node of an existing tree."""
+    if g is not None:
+        node.h_g = 0.0 if node.depth == c_d_max else g
+    if beta_vec is not None:
+        node.h_beta_vec[:] = beta_vec
+    for child in node.children:
+        if child is not None:
+            _fill_tree(child, c_d_max, g, beta_vec)
+
+
+class GenModel(base.Generative):
+    """Data-generating model and its prior (ref:30-420; plotting is out of scope)."""
+
+    def __init__(self, c_k, c_d_max=2, root=None, h_g=0.5, h_beta_vec=None, h_root=None, seed=None):
+        self.c_k = _check.pos_int(c_k, "c_k", ParameterFormatError)
+        self.c_d_max = _check.pos_int(c_d_max, "c_d_max", ParameterFormatError)
+        self.rng = np.random.default_rng(seed)
+        self.h_g = 0.5
+        self.h_beta_vec = np.ones(self.c_k) / 2
+        self.h_root = None
+        self.set_h_params(h_g, h_beta_vec, h_root)
+        self.root = _Node(0, self.c_k, self.h_g)
+        self.root.h_beta_vec[:] = self.h_beta_vec
+        self.root.leaf = True
+        self.set_params(root)
+
+    def get_constants(self):
+        return {"c_k": self.c_k, "c_d_max": self.c_d_max}
+
+    def set_h_params(self, h_g=None, h_beta_vec=None, h_root=None):
+        if h_g is not None:
+            self.h_g = _check.float_in_closed01(h_g, "h_g", ParameterFormatError)
+            if self.h_root is not None:
+                _fill_tree(self.h_root, self.c_d_max, g=self.h_g)
+        if h_beta_vec is not None:
+            _check.pos_floats(h_beta_vec, "h_beta_vec", ParameterFormatError)
+            self.h_beta_vec[:] = h_beta_vec
+            if self.h_root is not None:
+                _fill_tree(self.h_root, self.c_d_max, beta_vec=self.h_beta_vec)
+        if h_root is not None:
+            if type(h_root) is not _Node:
+                raise ParameterFormatError("h_root must be an instance of contexttree._Node")
+            if self.h_root is None:
+                self.h_root = _Node(0, self.c_k)
+            _copy_h_tree(self.h_root, h_root, self.c_k, self.c_d_max, self.h_g, self.h_beta_vec)
+        return self
+
+    def get_h_params(self):
+        return {"h_g": self.h_g, "h_beta_vec": self.h_beta_vec, "h_root": self.h_root}
+
+    def _gen_params(self, node, h_node, tree_fix):
+        """ref:101-145: the tree shape (unless ``tree_fix``) and the leaves' theta_vec, drawn top-down."""
+        g = self.h_g if h_node is None else h_node.h_g
+        beta_vec = self.h_beta_vec if h_node is None else h_node.h_beta_vec
+        node.h_g = 0.0 if node.depth == self.c_d_max else g
+        node.h_beta_vec[:] = beta_vec
+        if tree_fix:
+            if node.leaf:
+                node.theta_vec[:] = self.rng.dirichlet(beta_vec)
+            else:
+                for i in range(self.c_k):
+                    if node.children[i] is not None:
+                        self._gen_params(node.children[i], None if h_node is None else h_node.children[i], True)
+        elif node.depth == self.c_d_max or self.rng.random() > g:
+            node.theta_vec[:] = self.rng.dirichlet(beta_vec)
+            node.leaf = True
+        else:
+            node.leaf = False
+            for i in range(self.c_k):
+                if node.children[i] is None:
+                    node.children[i] = _Node(node.depth + 1, self.c_k)
+                self._gen_params(node.children[i], None if h_node is None else h_node.children[i], False)
+
+    def gen_params(self, tree_fix=False):
+        self._gen_params(self.root, self.h_root, tree_fix)
+        return self
+
+    def _set_params(self, node, orig):
+        """ref:147-161."""
+        node.h_g = orig.h_g
+        node.h_beta_vec[:] = orig.h_beta_vec
+        node.theta_vec[:] = orig.theta_vec
+        if node.depth == self.c_d_max:
+            node.leaf = True
+            node.h_g = 0.0
+        elif orig.leaf:
+            node.leaf = True
+        else:
+            node.leaf = False
+            for i in range(self.c_k):
+                if node.children[i] is None:
+                    node.children[i] = _Node(node.depth + 1, self.c_k)
+                self._set_params(node.children[i], orig.children[i])
+
+    def set_params(self, root=None):
+        if root is not None:
+            if type(root) is not _Node:
+                raise ParameterFormatError("root must be an instance of contexttree._Node")
+            self._set_params(self.root, root)
+        return self
+
+    def get_params(self):
+        return {"root": self.root}
+
+    def gen_sample(self, sample_length, initial_values=None):
+        """ref:323-355: the chain starts from ``initial_values`` (zeros by default), which are not returned."""
+        _check.pos_int(sample_length, "sample_length", DataFormatError)
+        x = np.zeros(sample_length + self.c_d_max, dtype=int)
+        if initial_values is not None:
+            _check.nonneg_ints(initial_values, "initial_values", DataFormatError)
+            _check.shape_consistency(initial_values.shape[0], "initial_values.shape[0]", self.c_d_max, "self.c_d_max",
+                                     DataFormatError)
+            if initial_values.max() >= self.c_k:
+                raise DataFormatError(f"initial_values.max() must smaller than c_k:{self.c_k}")
+            x[:self.c_d_max] = initial_values
+        for i in range(self.c_d_max, sample_length + self.c_d_max):
+            node = self.root
+            while not node.leaf:
+                node = node.children[x[i - node.depth - 1]]
+            x[i] = self.rng.choice(self.c_k, p=node.theta_vec)
+        return x[self.c_d_max:]
+
+    def save_sample(self, filename, sample_length, initial_values=None):
+        np.savez_compressed(filename, self.gen_sample(sample_length, initial_values))
+
+    def visualize_model(self, filename=None, format=None, sample_length=10):
+        _check.pos_int(sample_length, "sample_length", DataFormatError)
+        raise NotImplementedError(_ctree.PLOT_MSG)
+
+
+class LearnModel(base.Posterior, base.PredictiveMixin):
+    """Posterior and predictive distribution (ref:422-1067).  Positional parameters are the reference's; keyword-only
+    ``device`` selects the GPU.  The dense tables limit the shape to ``c_k <= 256`` and ``c_k ** (c_d_max + 1) <= 2 ** 24``
+    (``EngineLimitError`` beyond; the reference has no such limit).
+
+    The engine, and with it the GPU, is first needed when a posterior tree exists: at the first ``update_posterior`` or
+    ``pred_and_update`` - or already in the constructor (and in ``set_h0_params`` / ``set_hn_params``) when a tree is given
+    as ``h0_root`` / ``hn_root``, because it is scattered into the device tables at once.  Without a GPU those calls raise
+    ``EngineUnavailableError``; a model without a tree is built on the host alone."""
+
+    _ctree_pass_factory = None        # private test seam (tests/fake_contexttree_engine.py)
+
+    def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, device=None):
+        self.c_k = _check.pos_int(c_k, "c_k", ParameterFormatError)
+        self.c_d_max = _check.pos_int(c_d_max, "c_d_max", ParameterFormatError)
+        _ctree.check_limit(self.c_k, self.c_d_max)
+        self._device = device
+        self._engine = None
+        self._saved_tables = None
+        self._has_root = False
+        self._off = _ctree.offsets(self.c_k, self.c_d_max)
+
+        self.h0_g = h0_g
+        self.h0_beta_vec = np.ones(self.c_k) / 2
+        self.h0_root = None
+        self.hn_g = h0_g
+        self.hn_beta_vec = np.ones(self.c_k) / 2
+        self.p_theta_vec = np.ones(self.c_k) / self.c_k
+        self.set_h0_params(h0_g, h0_beta_vec, h0_root)
+
+    # ---- the engine and its tables ---------------------------------------------------------------------------------------
+    def _eng(self):
+        if self._engine is None:
+            make = self._ctree_pass_factory
+            self._engine = (make(self.c_k, self.c_d_max) if make is not None
+                            else _ctree.CtreePass(self.c_k, self.c_d_max, self._device))
+            if self._saved_tables is not None:
+                self._engine.set_tables(self._saved_tables)
+                self._saved_tables = None
+        return self._engine
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        if self._engine is not None and self._has_root:
+            state["_saved_tables"] = self._engine.get_tables()
+        state["_engine"] = None
+        return state
+
+    def get_constants(self):
+        return {"c_k": self.c_k, "c_d_max": self.c_d_max}
+
+    def _default_g(self, depth):
+        return 0.0 if depth == self.c_d_max else self.hn_g
+
+    @property
+    def hn_root(self):
+        """The posterior as the reference's ``_Node`` tree (a fresh copy: host work proportional to the existing nodes),
+        or ``None`` before the first update."""
+        if not self._has_root:
+            return None
+        t = self._eng().get_tables()
+        k, off, level = self.c_k, self._off, {}
+        for d in range(self.c_d_max + 1):
+            below = level
+            level = {}
+            for s in np.flatnonzero(t["exists"][off[d]:off[d + 1]]):
+                s = int(s)
+                node = _Node(d, k, float(t["g"][off[d] + s]))
+                node.h_beta_vec[:] = t["beta"][off[d] + s]
+                node.leaf = bool(t["leaf"][off[d] + s])
+                level[s] = node
+                if d > 0:
+                    below[s % k ** (d - 1)].children[s // k ** (d - 1)] = node
+            if d == 0:
+                root = level[0]
+        return root
+
+    def _scatter_tree(self, t, d, s, orig):
+        """ref:547-576 on the tables ``t`` (host copies): superpose ``orig`` on the existing node s of level d."""
+        k, D, off = self.c_k, self.c_d_max, self._off
+        i = off[d] + s
+        if orig is None:
+            for dd in range(d, D + 1):
+                idx = off[dd] + s + k ** d * np.arange(k ** (dd - d))
+                idx = idx[t["exists"][idx] != 0]
+                t["g"][idx] = self._default_g(dd)
+                t["beta"][idx] = self.hn_beta_vec
+            return
+        t["g"][i] = orig.h_g
+        t["beta"][i] = orig.h_beta_vec
+        if d == D:
+            t["leaf"][i] = 1
+            t["g"][i] = 0.0
+        elif orig.leaf:
+            t["leaf"][i] = 1
+        else:
+            t["leaf"][i] = 0
+            for c in range(k):
+                ci = off[d + 1] + s + c * k ** d
+                if not t["exists"][ci]:
+                    t["exists"][ci], t["g"][ci], t["beta"][ci], t["leaf"][ci] = 1, 0.5, 0.5, 0
+                self._scatter_tree(t, d + 1, s + c * k ** d, orig.children[c])
+
+    # ---- hyperparameters ---------------------------------------------------------------------------------------------------
+    def set_h0_params(self, h0_g=None, h0_beta_vec=None, h0_root=None):
+        if h0_g is not None:
+            self.h0_g = _check.float_in_closed01(h0_g, "h0_g", ParameterFormatError)
+            if self.h0_root is not None:
+                _fill_tree(self.h0_root, self.c_d_max, g=self.h0_g)
+        if h0_beta_vec is not None:
+            _check.pos_floats(h0_beta_vec, "h0_beta_vec", ParameterFormatError)
+            self.h0_beta_vec[:] = h0_beta_vec
+            if self.h0_root is not None:
+                _fill_tree(self.h0_root, self.c_d_max, beta_vec=self.h0_beta_vec)
+        if h0_root is not None:
+            if type(h0_root) is not _Node:
+                raise ParameterFormatError("h0_root must be an instance of contexttree._Node")
+            if self.h0_root is None:
+                self.h0_root = _Node(0, self.c_k)
+            _copy_h_tree(self.h0_root, h0_root, self.c_k, self.c_d_max, self.h0_g, self.h0_beta_vec)
+        self.reset_hn_params()
+        return self
+
+    def get_h0_params(self):
+        return {"h0_g": self.h0_g, "h0_beta_vec": self.h0_beta_vec, "h0_root": self.h0_root}
+
+    def set_hn_params(self, hn_g=None, hn_beta_vec=None, hn_root=None):
+        if hn_g is not None:
+            self.hn_g = _check.float_in_closed01(hn_g, "hn_g", ParameterFormatError)
+            if self._has_root:
+                self._eng().fill_existing(g=self.hn_g)
+        if hn_beta_vec is not None:
+            _check.pos_floats(hn_beta_vec, "hn_beta_vec", ParameterFormatError)
+            self.hn_beta_vec[:] = hn_beta_vec
+            if self._has_root:
+                self._eng().fill_existing(beta=self.hn_beta_vec)
+        if hn_root is not None:
+            if type(hn_root) is not _Node:
+                raise ParameterFormatError("hn_root must be an instance of contexttree._Node")
+            eng = self._eng()
+            if not self._has_root:
+                eng.clear()
+            t = eng.get_tables()
+            if not self._has_root:
+                t["exists"][0], t["g"][0], t["beta"][0], t["leaf"][0] = 1, 0.5, 0.5, 0
+            self._scatter_tree(t, 0, 0, hn_root)
+            eng.set_tables(t)
+            self._has_root = True
+        self.calc_pred_dist(np.zeros(self.c_d_max, dtype=int))
+        return self
+
+    def get_hn_params(self):
+        return {"hn_g": self.hn_g, "hn_beta_vec": self.hn_beta_vec, "hn_root": self.hn_root}
+
+    # ---- learning ----------------------------------------------------------------------------------------------------------
+    def update_posterior(self, x):
+        """ref:712-731 in batch form; a refused sample changes nothing."""
+        if _check._is_int(x) and x >= 0:
+            x = np.asarray([x])
+        if _check.sample_kind(x) != "i":
+            raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
+        if (x.numel() if hasattr(x, "numel") else x.size) == 0:
+            np.max(np.zeros(0))          # the reference's x.max() of an empty sample: ValueError
+        eng = self._eng()
+        xd = eng.adopt(x)
+        if not self._has_root:
+            eng.clear()
+        n, bad = eng.update(xd, self.hn_g, self.hn_beta_vec)
+        if bad > 0:
+            if eng.any_negative(xd):
+                raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
+            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+        self._has_root = True
+        return self
+
+    def estimate_params(self, loss="0-1", visualize=True, filename=None, format=None):
+        """The MAP tree (ref:733-831) from ``ctree_map``'s table; only the pruned tree is built.  Plotting is out of scope:
+        pass ``visualize=False``.  Unlike the reference, the default-valued nodes that its sweep appends to ``hn_root`` are
+        not added to the posterior."""
+        if loss != "0-1":
+            raise CriteriaError("Unsupported loss function! This function supports only \"0-1\".")
+        if visualize:
+            raise NotImplementedError(_ctree.PLOT_MSG)
+        eng = self._eng()
+        if not self._has_root:
+            eng.clear()
+            eng.scatter([0], [self.hn_g], [self.hn_beta_vec], [1], [0])
+            self._has_root = True
+        ml = eng.map_leaf(self.hn_g)
+        t = eng.get_tables()
+        k, D, off = self.c_k, self.c_d_max, self._off
+
+        def build(d, s, parent_g):
+            i = off[d] + s
+            node = _Node(d, k)
+            if t["exists"][i]:
+                node.h_g, beta = float(t["g"][i]), t["beta"][i]
+            else:
+                # (ref:755-762: a missing child that its parent's rule makes a leaf keeps hn_g even at the maximal depth)
+                by_rule = d == D and parent_g is not None and 1.0 - parent_g > parent_g * self.hn_g ** (
+                    (k ** (D - d + 1) - 1) / (k - 1) - 1)
+                node.h_g, beta = (self.hn_g if d < D or by_rule else 0.0), self.hn_beta_vec
+            node.h_beta_vec[:] = beta
+            if np.all(beta > 1):
+                node.theta_vec[:] = (beta - 1) / (np.sum(beta) - k)
+            else:
+                warnings.warn("MAP estimate of theta_vec doesn't exist for the current h_beta_vec.", ResultWarning)
+                node.theta_vec = None
+            if ml[i]:
+                node.leaf = True
+            else:
+                below = float(t["g"][i]) if t["exists"][i] else None
+                for c in range(k):
+                    node.children[c] = build(d + 1, s + c * k ** d, below)
+            return node
+
+        return build(0, 0, None)
+
+    def visualize_posterior(self, filename=None, format=None, h_params=False):
+        raise NotImplementedError(_ctree.PLOT_MSG)
+
+    # ---- prediction --------------------------------------------------------------------------------------------------------
+    def get_p_params(self):
+        return {"p_theta_vec": self.p_theta_vec}
+
+    def _check_context(self, x):
+        if not (_check._arr_kind(x) == "i" and x.ndim == 1 and np.all(x >= 0)):
+            raise DataFormatError("x" + _INT_VEC_MSG)
+        if x.max() >= self.c_k:
+            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+
+    def _path(self, x):
+        """The D + 1 (or fewer) rows that the context before x[-1] selects, missing ones created with the defaults as
+        ref:956-965 does.  Returns (indices, g, beta, leaf)."""
+        i = x.shape[0] - 1
+        depth = min(i, self.c_d_max)
+        idx, key = [0], 0
+        for d in range(depth):
+            key += int(x[i - d - 1]) * self.c_k ** d
+            idx.append(self._off[d + 1] + key)
+        g, beta, exists, leaf = self._eng().gather(idx)
+        g, beta, leaf = g.copy(), beta.copy(), leaf.copy()
+        for d in range(depth + 1):
+            if not exists[d]:
+                g[d], beta[d], leaf[d] = self._default_g(d), self.hn_beta_vec, d == self.c_d_max
+        return idx, g, beta, leaf
+
+    def calc_pred_dist(self, x):
+        """ref:954-989: the mixture over the path of the context x[:-1] (x[-1] is the position to predict)."""
+        self._check_context(x)
+        if not self._has_root:
+            self.p_theta_vec[:] = self.hn_beta_vec / self.hn_beta_vec.sum()
+            return self
+        idx, g, beta, leaf = self._path(x)
+        p = beta[-1] / beta[-1].sum()
+        for d in range(len(idx) - 2, -1, -1):
+            p = (1 - g[d]) * beta[d] / beta[d].sum() + g[d] * p
+        self.p_theta_vec[:] = p
+        self._eng().scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
+        return self
+
+    def make_prediction(self, loss="KL"):
+        if loss == "KL":
+            return self.p_theta_vec
+        if loss == "0-1":
+            return np.argmax(self.p_theta_vec)
+        raise CriteriaError("Unsupported loss function! This function supports \"0-1\" and \"KL\".")
+
+    def pred_and_update(self, x, loss="KL"):
+        """ref:1016-1067: predict x[-1] from the context before it, then fold it in; one path, host work."""
+        self._check_context(x)
+        eng = self._eng()
+        if not self._has_root:
+            eng.clear()
+            eng.scatter([0], [self.hn_g], [self.hn_beta_vec], [1], [0])
+            self._has_root = True
+        idx, g, beta, leaf = self._path(x)
+        a = int(x[-1])
+        p = beta[-1] / beta[-1].sum()
+        beta[-1, a] += 1
+        for d in range(len(idx) - 2, -1, -1):
+            own = beta[d] / beta[d].sum()
+            beta[d, a] += 1
+            mixed = (1 - g[d]) * own + g[d] * p
+            g[d] = g[d] * p[a] / mixed[a]
+            p = mixed
+        self.p_theta_vec[:] = p
+        eng.scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
+        return self.make_prediction(loss=loss)
