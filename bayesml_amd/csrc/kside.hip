@@ -1,5 +1,6 @@
 // K-sized linear algebra of the posterior update that the torch K-side would otherwise hand to MAGMA / rocSOLVER:
-// one Cholesky factorisation and one triangular inverse per component, LDS-resident (D <= 128: 129 KB of the 160 KB).
+// one Cholesky factorisation and one triangular inverse per component, LDS-resident (D <= 128: 152 KB of the 160 KB), for
+// D > 32 in blocks of 16 on the f64 matrix pipe.
 //
 // Replaces, per VB iteration, what the reference does with np.linalg.inv + two slogdet per component
 // (bayesml/gaussianmixture/_gaussianmixture.py:746-756, 769): from W^-1 = G G^T it yields G (-> u^-1 = G / sqrt(nu)),
@@ -13,6 +14,148 @@
 #include <vector>
 
 namespace gmmvb {
+
+// ---- factor and invert in blocks of 16 on v_mfma_f64_16x16x4_f64 (D > 32) ----------------------------------------------
+// The matrix lives in LDS as [PD][PD + 1] doubles, PD = D rounded up to 16, lower triangle filled, the rest zero, with an
+// identity corner in the padding (rows and columns >= D): no lane ever takes the square root or the reciprocal of a
+// padding zero, and the padding never mixes with the D x D part.  dinv [PD / 16][16][17] receives the inverses of the
+// factor's diagonal blocks.  NW waves (64 NW threads) call these together; tiles are dealt out per wave.
+// MFMA lane map (lane l: li = l & 15, lg = l >> 4): a = X[li][p + lg], b = Y[p + lg][li], result register r is row
+// lg + 4 r, column li of the tile.
+constexpr int kDinvLd = 17, kDinvSize = 16 * kDinvLd;
+
+__device__ __forceinline__ double lane_bcast(double v, int src) {          // src: a constant after unrolling
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+
+// One wave: Cholesky of the 16 x 16 diagonal block at (j0, j0) in registers - lane i (and its three copies i + 16 g, which
+// compute the same and store nothing) holds row i; the column steps are those of the unblocked loop, with lane
+// broadcasts instead of barriers - then the block's inverse, lane j holding column j.  A non-positive pivot leaves NaN
+// in its column and in everything right of and below it, as the unblocked loop does.
+__device__ __forceinline__ void diag_block_factor(double* mat, int ld, int j0, double* dinv) {
+    const int lane = threadIdx.x & 63, i = lane & 15;
+    double x[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) x[c] = c <= i ? mat[(j0 + i) * ld + j0 + c] : 0.0;
+    double inv_own = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const double d = sqrt(lane_bcast(x[j], j));
+        const double inv = 1.0 / d;
+        x[j] = i == j ? d : (i > j ? x[j] * inv : 0.0);
+        inv_own = i == j ? inv : inv_own;
+#pragma unroll
+        for (int c = j + 1; c < 16; ++c) x[c] = fma(-x[j], lane_bcast(x[j], c), x[c]);      // (used for i >= c only)
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) mat[(j0 + i) * ld + j0 + c] = x[c];
+    }
+    // inverse by forward substitution, column i of it in lane i: z[r] = -(sum_{p < r} L[r][p] z[p]) / L[r][r], with L[r][p]
+    // read back from LDS (one address for the whole wave), so that x[] need not stay in registers beside z[]
+    double z[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const double inv_r = lane_bcast(inv_own, r);
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < r; ++p) s = fma(mat[(j0 + r) * ld + j0 + p], z[p], s);
+        z[r] = i < r ? -s * inv_r : (i == r ? inv_r : 0.0);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dinv[r * kDinvLd + i] = z[r];
+    }
+}
+
+// Right-looking Cholesky, NB = 16: the diagonal block in one wave's registers, the panel below it as A21 L11^-T and the
+// trailing update C -= L21 L21^T over the lower tiles on the matrix pipe (the tile is the MFMA's C operand and -L21 its A
+// operand, so every element is still fma(-l_ij, l_cj, a_ic) column by column).  Wave 0 takes the next diagonal tile of
+// the trailing update and factorises it at once, beside the other waves' tiles: two barriers per block.
+template <int NW>
+__device__ __forceinline__ void blocked_cholesky(double* mat, int ld, int ntl, double* dinv) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    auto syrk_tile = [&](int rt, int ct, int j0) {
+        d4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = mat[(16 * rt + lg + 4 * r) * ld + 16 * ct + li];
+#pragma unroll
+        for (int p = 0; p < 16; p += 4)
+            acc = mfma_f64(-mat[(16 * rt + li) * ld + j0 + p + lg], mat[(16 * ct + li) * ld + j0 + p + lg], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mat[(16 * rt + lg + 4 * r) * ld + 16 * ct + li] = acc[r];
+    };
+    for (int kb = 0; kb < ntl; ++kb) {
+        if (wv == 0) {
+            if (kb > 0) syrk_tile(kb, kb, 16 * (kb - 1));
+            diag_block_factor(mat, ld, 16 * kb, dinv + kb * kDinvSize);
+        } else if (kb > 0) {
+            int t = 0;
+            for (int rt = kb + 1; rt < ntl; ++rt)
+                for (int ct = kb; ct <= rt; ++ct, ++t)
+                    if (t % (NW - 1) == wv - 1) syrk_tile(rt, ct, 16 * (kb - 1));
+        }
+        __syncthreads();
+        const int j0 = 16 * kb;
+        const double* di = dinv + kb * kDinvSize;
+        for (int rt = kb + 1 + wv; rt < ntl; rt += NW) {          // panel: L21 = A21 L11^-T
+            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int p = 0; p < 16; p += 4)
+                acc = mfma_f64(mat[(16 * rt + li) * ld + j0 + p + lg], di[li * kDinvLd + p + lg], acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mat[(16 * rt + lg + 4 * r) * ld + j0 + li] = acc[r];
+        }
+        __syncthreads();
+    }
+}
+
+// In-place inverse of the blocked factor: the diagonal blocks' inverses exist (dinv); T = G21 X11 for every block column
+// in one pass, then block column by block column, last first, X21 = -X22 T with X22 already inverted.  Everybody must
+// have finished reading the factor before the call.
+template <int NW>
+__device__ __forceinline__ void blocked_tri_inverse(double* mat, int ld, int ntl, const double* dinv) {
+    static_assert(NW >= 8, "one wave per tile row of a block column");
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    for (int kb = wv; kb < ntl; kb += NW) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            mat[(16 * kb + lg + 4 * r) * ld + 16 * kb + li] = dinv[kb * kDinvSize + (lg + 4 * r) * kDinvLd + li];
+    }
+    {
+        int t = 0;
+        for (int kb = 0; kb + 1 < ntl; ++kb)
+            for (int rt = kb + 1; rt < ntl; ++rt, ++t) {
+                if (t % NW != wv) continue;
+                const double* di = dinv + kb * kDinvSize;
+                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int p = 0; p < 16; p += 4)
+                    acc = mfma_f64(mat[(16 * rt + li) * ld + 16 * kb + p + lg], di[(p + lg) * kDinvLd + li], acc);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mat[(16 * rt + lg + 4 * r) * ld + 16 * kb + li] = acc[r];
+            }
+    }
+    __syncthreads();
+    for (int kb = ntl - 2; kb >= 0; --kb) {
+        const int rt = kb + 1 + wv;
+        d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+        if (rt < ntl) {
+            for (int ct = kb + 1; ct <= rt; ++ct)
+#pragma unroll
+                for (int p = 0; p < 16; p += 4)
+                    acc = mfma_f64(-mat[(16 * rt + li) * ld + 16 * ct + p + lg], mat[(16 * ct + p + lg) * ld + 16 * kb + li], acc);
+        }
+        __syncthreads();
+        if (rt < ntl) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mat[(16 * rt + lg + 4 * r) * ld + 16 * kb + li] = acc[r];
+        }
+        __syncthreads();
+    }
+}
 
 // One workgroup per matrix.  a [K][D][D] symmetric positive definite (row-major; only the lower triangle is read).
 // g, g_inv [K][D][D] lower triangular (upper part zero filled); logdet [K] = 2 sum_j ln g_jj.
@@ -79,6 +222,38 @@ __global__ __launch_bounds__(256) void chol_inv_kernel(const double* __restrict_
         __syncthreads();
     }
     for (int e = tid; e < D * D; e += 256) {
+        const int i = e / D, j = e - i * D;
+        g_inv[base + e] = sm[i * ld + j];
+    }
+}
+
+// The same for D > 32 on the blocked routines above: sixteen waves, sm = [PD][PD + 1] | dinv [PD / 16][16][17].
+__global__ __launch_bounds__(1024) void chol_inv_blocked_kernel(const double* __restrict__ a, int D, double* __restrict__ g,
+                                                                double* __restrict__ g_inv, double* __restrict__ logdet) {
+    extern __shared__ double sm[];
+    const int PD = (D + 15) & ~15, ld = PD + 1, ntl = PD >> 4;
+    double* dinv = sm + PD * ld;
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * D * D;
+    for (int e = tid; e < PD * PD; e += 1024) {
+        const int i = e / PD, j = e - i * PD;
+        sm[i * ld + j] = (i < D && j < D) ? (j <= i ? a[base + (int64_t)i * D + j] : 0.0) : (i == j ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    blocked_cholesky<16>(sm, ld, ntl, dinv);
+    for (int e = tid; e < D * D; e += 1024) {
+        const int i = e / D, j = e - i * D;
+        g[base + e] = sm[i * ld + j];
+    }
+    if (tid < 64) {          // ln det = 2 sum ln g_jj (one wave, fixed order)
+        double s = 0.0;
+        for (int j = tid; j < D; j += 64) s += log(sm[j * ld + j]);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (tid == 0) logdet[blockIdx.x] = 2.0 * s;
+    }
+    __syncthreads();
+    blocked_tri_inverse<16>(sm, ld, ntl, dinv);
+    for (int e = tid; e < D * D; e += 1024) {
         const int i = e / D, j = e - i * D;
         g_inv[base + e] = sm[i * ld + j];
     }
@@ -313,32 +488,37 @@ __device__ __forceinline__ void block_sum_n(double (&v)[NV], double* red /*[NT /
         for (int q = 0; q < NV; ++q) red[(threadIdx.x >> 6) * NV + q] = v[q];
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        double t = 0.0;
+    for (int q = 0; q < NV; ++q) v[q] = 0.0;
+    // (four waves' results at a time: unrolled, sixteen waves' 16 NV reads are issued at once and spill)
+#pragma unroll 1
+    for (int w = 0; w < NT / 64; w += 4)
 #pragma unroll
-        for (int w = 0; w < NT / 64; w += 4)
-            t += (red[w * NV + q] + red[(w + 1) * NV + q]) + (red[(w + 2) * NV + q] + red[(w + 3) * NV + q]);
-        v[q] = t;
-    }
+        for (int q = 0; q < NV; ++q)
+            v[q] += (red[w * NV + q] + red[(w + 1) * NV + q]) + (red[(w + 2) * NV + q] + red[(w + 3) * NV + q]);
 }
 
-// NT threads per component: 1024 for D > 32 (sixteen waves hide the LDS latency of the factorisation's short dependent
-// steps: 0.61 -> see DESIGN.md 4d), 256 below.
+// NT threads per component: 1024 for D > 32 (sixteen waves for the passes over the D x D statistics and for the tiles of
+// the blocked factorisation, inverse and W': DESIGN.md 4d), 256 with the column loops below.
 template <int NT>
 __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView pr, PostView q, PostView qn,
                                                          const double* __restrict__ stats, const double* __restrict__ pivot,
                                                          double* __restrict__ s_prev, double* __restrict__ ns_out,
                                                          double* __restrict__ x_bar_out, double* __restrict__ s_out,
                                                          double* __restrict__ partials /*[K][kPartials]*/) {
-    extern __shared__ double sm[];           // mat [D][D + 1] | abar, xbar, dev0, dq, dm [D] each | red [32]
-    const int ld = D + 1;
+    // mat [PD][PD + 1] | abar, xbar, dev0, dq, dm [D] each | red [64] | dinv [PD / 16][16][17] (wide only)
+    // PD = D on the narrow path, D rounded up to the block size 16 on the wide one
+    extern __shared__ double sm[];
+    constexpr bool WIDE = NT == 1024;
+    const int PD = WIDE ? (D + 15) & ~15 : D;
+    const int ld = PD + 1;
     double* mat = sm;
-    double* abar = sm + (size_t)D * ld;
+    double* abar = sm + (size_t)PD * ld;
     double* xbar = abar + D;
     double* dev0 = xbar + D;
     double* dq = dev0 + D;
     double* dm = dq + D;
     double* red = dm + D;          // [NT / 64 * 4]
+    double* dinv = red + 64;
     const int tid = threadIdx.x, k = blockIdx.x;
     const int64_t vb = (int64_t)k * D, mb = (int64_t)k * D * D;
     const double LN_2PI = 1.8378770664093454835606594728112, LN_2 = 0.69314718055994530941723212145818,
@@ -364,13 +544,12 @@ __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView 
     const double kapn = kap0 + ns, nun = nu0 + ns, aln = al0 + ns;
     const double coef = kap0 * ns / kapn;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};          // tr(S nu W), dq' nu W dq, dm' nu W dm, tr(W0^-1 nu W)
-    for (int e = tid; e < D * D; e += NT) {
+    auto stat_elem = [&](int e, double sraw, double wq, double w0) {
         const int i = e / D, j = e - i * D;
-        const double sij = pos ? B[e] / safe - abar[i] * abar[j] : s_prev[mb + e];
+        const double sij = pos ? sraw / safe - abar[i] * abar[j] : sraw;
         s_out[mb + e] = sij;
         s_prev[mb + e] = sij;
-        const double ew = nuq * q.w[mb + e];
-        const double w0 = pr.w_inv[mb + e];
+        const double ew = nuq * wq;
         acc[0] = fma(sij, ew, acc[0]);
         acc[1] = fma(dq[i] * dq[j], ew, acc[1]);
         acc[2] = fma(dm[i] * dm[j], ew, acc[2]);
@@ -378,6 +557,33 @@ __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView 
         const double wn = w0 + ns * sij + coef * (dev0[i] * dev0[j]);
         qn.w_inv[mb + e] = wn;
         mat[i * ld + j] = j <= i ? wn : 0.0;
+    };
+    if constexpr (WIDE) {
+        // four elements' loads are issued together (the compiler cannot move a load over the stores of the element before:
+        // the views may alias), every thread still adds its elements in index order
+        const int DD = D * D;
+        for (int e0 = tid; e0 < DD; e0 += 4 * NT) {
+            double sr[4], wq[4], w0[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int e = e0 + u * NT;
+                const bool ok = e < DD;
+                sr[u] = ok ? (pos ? B[e] : s_prev[mb + e]) : 0.0;
+                wq[u] = ok ? q.w[mb + e] : 0.0;
+                w0[u] = ok ? pr.w_inv[mb + e] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (e0 + u * NT < DD) stat_elem(e0 + u * NT, sr[u], wq[u], w0[u]);
+        }
+        // identity corner of the padding (block_sum_n below holds the barrier before the factorisation)
+        if (PD != D)
+            for (int e = tid; e < PD * PD; e += NT) {
+                const int i = e / PD, j = e - i * PD;
+                if (i >= D || j >= D) mat[i * ld + j] = i == j ? 1.0 : 0.0;
+            }
+    } else {
+        for (int e = tid; e < D * D; e += NT) stat_elem(e, pos ? B[e] : s_prev[mb + e], q.w[mb + e], pr.w_inv[mb + e]);
     }
     block_sum_n<4, NT>(acc, red);
     if (tid == 0) {
@@ -399,23 +605,29 @@ __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView 
     }
     for (int i = tid; i < D; i += NT) qn.m[vb + i] = (kap0 * pr.m[vb + i] + ns * xbar[i]) / kapn;
     __syncthreads();
-    // ---- Cholesky of W'^-1 in LDS (as in chol_inv_kernel).  (Round 4 measured a version blocked by 16 columns - diagonal
-    // block in one wave's registers, panel solve with a thread per row, trailing update from 16-term dot products, and the
-    // inverse block column by block column: 24 + 32 barriers instead of 384 + 256 - at 0.312 ms per launch against 0.298:
-    // the 128 barrier-separated columns are not what the kernel's time is made of.  Not kept.)
-    constexpr int TG = NT == 1024 ? 32 : 16;                  // the trailing update runs on a TG x TG thread grid
-    const int ti = tid / TG, tj = tid % TG;
-    for (int j = 0; j < D; ++j) {
-        if (tid == 0) mat[j * ld + j] = sqrt(mat[j * ld + j]);
-        __syncthreads();
-        const double inv = 1.0 / mat[j * ld + j];
-        for (int i = j + 1 + tid; i < D; i += NT) mat[i * ld + j] *= inv;
-        __syncthreads();
-        for (int i = j + 1 + ti; i < D; i += TG) {
-            const double lij = mat[i * ld + j];
-            for (int c = j + 1 + tj; c <= i; c += TG) mat[i * ld + c] = fma(-lij, mat[c * ld + j], mat[i * ld + c]);
+    // ---- Cholesky of W'^-1 in LDS.  Wide path: blocks of 16 on the f64 matrix pipe (blocked_cholesky above).
+    // Measured per phase at K = 64, D = 128 (profiles/kside_phases.md), column loops -> blocks: Cholesky 107 -> 38 us, inverse
+    // 106 -> 12 us, W' and u' 42 -> 11 us, the kernel 286 -> 90 us.  The column loops took both operands of every FMA from LDS
+    // between 384 + 256 barriers; a round-4 variant that only blocked the barriers away (16-term dot products, a thread per
+    // row in the panel solve) was no faster, 0.312 against 0.298 ms: the LDS traffic per FMA is what the time was made of.
+    // What remains of the factorisation is the diagonal block in one wave's registers, 4.8 us per block.
+    if constexpr (WIDE) {
+        blocked_cholesky<NT / 64>(mat, ld, PD >> 4, dinv);
+    } else {
+        constexpr int TG = 16;                                // the trailing update runs on a TG x TG thread grid
+        const int ti = tid / TG, tj = tid % TG;
+        for (int j = 0; j < D; ++j) {
+            if (tid == 0) mat[j * ld + j] = sqrt(mat[j * ld + j]);
+            __syncthreads();
+            const double inv = 1.0 / mat[j * ld + j];
+            for (int i = j + 1 + tid; i < D; i += NT) mat[i * ld + j] *= inv;
+            __syncthreads();
+            for (int i = j + 1 + ti; i < D; i += TG) {
+                const double lij = mat[i * ld + j];
+                for (int c = j + 1 + tj; c <= i; c += TG) mat[i * ld + c] = fma(-lij, mat[c * ld + j], mat[i * ld + c]);
+            }
+            __syncthreads();
         }
-        __syncthreads();
     }
     const double sq = sqrt(nun), isq = 1.0 / sq;
     for (int e = tid; e < D * D; e += NT) {
@@ -448,32 +660,61 @@ __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView 
         qn.c[k] = elp + 0.5 * (eld - D * LN_2PI - D / kapn);
     }
     __syncthreads();
-    // ---- in-place inverse of the factor: column j from the columns right of it; SEG threads share a row's dot product
-    constexpr int SEG = NT / 128;                             // D <= 128 rows
-    const int rl = tid / SEG, seg = tid % SEG;
-    for (int j = D - 1; j >= 0; --j) {
-        const double xjj = 1.0 / mat[j * ld + j];
-        const int i = j + 1 + rl;
-        double v = 0.0;
-        if (i < D)
-            for (int p = j + 1 + seg; p <= i; p += SEG) v = fma(mat[i * ld + p], mat[p * ld + j], v);
+    if constexpr (WIDE) {
+        // ---- in-place inverse of the factor, block column by block column; u' = sqrt(nu') G^-1
+        blocked_tri_inverse<NT / 64>(mat, ld, PD >> 4, dinv);
+        for (int e = tid; e < D * D; e += NT) {
+            const int i = e / D, j = e - i * D;
+            qn.u[mb + e] = mat[i * ld + j] * sq;
+        }
+        // W' = G^-T G^-1: the upper tiles only, heaviest first, dealt out over the waves; the contraction of tile (ta, tb)
+        // starts at the tile's first non-zero row 16 tb (the identity corner adds nothing to the D x D part).  w[i][j] and
+        // w[j][i] come from the same register (diagonal tiles: from the registers on and above the diagonal): exactly symmetric.
+        const int lane = tid & 63, wv = tid >> 6, li = lane & 15, lg = lane >> 4, ntl = PD >> 4;
+        int t = 0;
+        for (int tb = 0; tb < ntl; ++tb)
+            for (int ta = 0; ta <= tb; ++ta, ++t) {
+                if (t % (NT / 64) != wv) continue;
+                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+                for (int p = 16 * tb; p < PD; p += 4)
+                    acc = mfma_f64(mat[(p + lg) * ld + 16 * ta + li], mat[(p + lg) * ld + 16 * tb + li], acc);
 #pragma unroll
-        for (int o = 1; o < SEG; o <<= 1) v += __shfl_xor(v, o);
-        v = -v * xjj;
-        __syncthreads();
-        if (i < D && seg == 0) mat[i * ld + j] = v;
-        if (tid == 0) mat[j * ld + j] = xjj;
-        __syncthreads();
-    }
-    // u' = sqrt(nu') G^-1 and W' = G^-T G^-1 (upper triangle computed, mirrored: exactly symmetric)
-    for (int e = tid; e < D * D; e += NT) {
-        const int i = e / D, j = e - i * D;
-        qn.u[mb + e] = mat[i * ld + j] * sq;
-        if (i <= j) {
-            double w = 0.0;
-            for (int p = j; p < D; ++p) w = fma(mat[p * ld + i], mat[p * ld + j], w);
-            qn.w[mb + e] = w;
-            qn.w[mb + (int64_t)j * D + i] = w;
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * ta + lg + 4 * r, j = 16 * tb + li;
+                    if (i <= j && j < D) {
+                        qn.w[mb + (int64_t)i * D + j] = acc[r];
+                        qn.w[mb + (int64_t)j * D + i] = acc[r];
+                    }
+                }
+            }
+    } else {
+        // ---- in-place inverse of the factor: column j from the columns right of it; SEG threads share a row's dot product
+        constexpr int SEG = NT / 128;                             // D <= 128 rows
+        const int rl = tid / SEG, seg = tid % SEG;
+        for (int j = D - 1; j >= 0; --j) {
+            const double xjj = 1.0 / mat[j * ld + j];
+            const int i = j + 1 + rl;
+            double v = 0.0;
+            if (i < D)
+                for (int p = j + 1 + seg; p <= i; p += SEG) v = fma(mat[i * ld + p], mat[p * ld + j], v);
+#pragma unroll
+            for (int o = 1; o < SEG; o <<= 1) v += __shfl_xor(v, o);
+            v = -v * xjj;
+            __syncthreads();
+            if (i < D && seg == 0) mat[i * ld + j] = v;
+            if (tid == 0) mat[j * ld + j] = xjj;
+            __syncthreads();
+        }
+        // u' = sqrt(nu') G^-1 and W' = G^-T G^-1 (upper triangle computed, mirrored: exactly symmetric)
+        for (int e = tid; e < D * D; e += NT) {
+            const int i = e / D, j = e - i * D;
+            qn.u[mb + e] = mat[i * ld + j] * sq;
+            if (i <= j) {
+                double w = 0.0;
+                for (int p = j; p < D; ++p) w = fma(mat[p * ld + i], mat[p * ld + j], w);
+                qn.w[mb + e] = w;
+                qn.w[mb + (int64_t)j * D + i] = w;
+            }
         }
     }
 }
@@ -589,13 +830,21 @@ extern "C" int gmmvb_kside_factor(int K, int D, const double* w_inv_dev, double*
     if (K < 1 || D < 1) return fail(GMMVB_EINVAL, "K and D must be positive");
     if (D > 128) return fail(GMMVB_EUNSUPPORTED, "gmmvb_kside_factor: D > 128 (the factor is kept in LDS)");
     if (!w_inv_dev || !g_dev || !g_inv_dev || !logdet_dev) return fail(GMMVB_EINVAL, "null argument");
-    const size_t lds = (size_t)D * (D + 1) * sizeof(double);
-    {
-        hipError_t e = ensure_dynamic_lds((const void*)chol_inv_kernel, (size_t)128 * 129 * sizeof(double));
+    if (D > 32) {
+        const int PD = (D + 15) & ~15;
+        const size_t lds = ((size_t)PD * (PD + 1) + (size_t)(PD / 16) * kDinvSize) * sizeof(double);
+        hipError_t e = ensure_dynamic_lds((const void*)chol_inv_blocked_kernel,
+                                          ((size_t)128 * 129 + (size_t)8 * kDinvSize) * sizeof(double));
+        if (e != hipSuccess) return fail(GMMVB_EHIP, "hipFuncSetAttribute(chol_inv_blocked_kernel)", e);
+        hipLaunchKernelGGL(chol_inv_blocked_kernel, dim3(K), dim3(1024), lds, (hipStream_t)stream, w_inv_dev, D, g_dev,
+                           g_inv_dev, logdet_dev);
+    } else {
+        const size_t lds = (size_t)D * (D + 1) * sizeof(double);
+        hipError_t e = ensure_dynamic_lds((const void*)chol_inv_kernel, (size_t)32 * 33 * sizeof(double));
         if (e != hipSuccess) return fail(GMMVB_EHIP, "hipFuncSetAttribute(chol_inv_kernel)", e);
+        hipLaunchKernelGGL(chol_inv_kernel, dim3(K), dim3(256), lds, (hipStream_t)stream, w_inv_dev, D, g_dev, g_inv_dev,
+                           logdet_dev);
     }
-    hipLaunchKernelGGL(chol_inv_kernel, dim3(K), dim3(256), lds, (hipStream_t)stream, w_inv_dev, D, g_dev, g_inv_dev,
-                       logdet_dev);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GMMVB_EHIP, "chol_inv_kernel launch", e);
     return GMMVB_OK;
@@ -645,8 +894,9 @@ extern "C" int gmmvb_kside_step(int K, int D, const gmmvb_prior_view* prior, con
     std::memcpy(&qa, q, sizeof(qa));
     std::memcpy(&qb, q_next, sizeof(qb));
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)D * (D + 1) + 5 * (size_t)D + 64) * sizeof(double);
     const bool wide = D > 32;
+    const int PD = wide ? (D + 15) & ~15 : D;                 // (wide: padded to the block size, plus the diagonal inverses)
+    const size_t lds = ((size_t)PD * (PD + 1) + 5 * (size_t)D + 64 + (wide ? (size_t)(PD / 16) * kDinvSize : 0)) * sizeof(double);
     {
         hipError_t e = ensure_dynamic_lds(wide ? (const void*)kside_step_kernel<1024> : (const void*)kside_step_kernel<256>, lds);
         if (e != hipSuccess) return fail(GMMVB_EHIP, "hipFuncSetAttribute(kside_step_kernel)", e);
