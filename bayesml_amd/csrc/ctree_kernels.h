@@ -104,6 +104,19 @@ __global__ __launch_bounds__(kThreads) void count_combine_kernel(const int64_t* 
 // the size of the result.  Small arguments keep the library's lgamma.  A row of at most kDirect new samples (the second of
 // two updates, say, on top of large b') is the rising-factorial form sum ln(b'_a + j) - sum ln(sum b' + j) itself: there
 // G(b' + n') and G(b') would agree in nearly all their digits.
+//
+// They do the same for any batch that is small next to a prior total V = sum b' that is already in the series (an update of
+// a trained model): each G is of the size of sum v ln(v / V), their difference of the size of n' ln V.  So from
+// V >= kStirling on, the row is a sum of per-argument differences, in which the -n terms cancel exactly and n_a ln v_a
+// joins its share n_a ln V of the total's logarithm:
+//     lnG(v + n) - lnG(v) - n ln V + n = (v + n - 1/2) log1p(n / v) + n ln(v / V) + t(v + n) - t(v)          (v >= kStirling)
+//     lnG(V + N) - lnG(V) - N ln V + N = (V + N - 1/2) log1p(N / V) + t(V + N) - t(V)                         (the total)
+// and an argument below kStirling keeps lgamma on the side(s) where it is small:
+//     (v + n - 1/2) ln((v + n) / V) + (v - 1/2) ln V - v + ln(2 pi)/2 + t(v + n) - lnG(v)              (v < kStirling <= v + n)
+//     lnG(v + n) - lnG(v) - n (ln V - 1)                                                                (v + n < kStirling)
+// Every term is of the size of the lnG differences it stands for (tests/test_gpu_contexttree_rows.py holds the sweep to
+// 64 eps of their sum against an exact evaluation).  A first update from a small prior (V < kStirling) keeps
+// G(b' + n') - G(b').
 constexpr double kStirling = 64.0;        // t(x) below is exact to 1e-18 from here on
 constexpr int kDirect = 64;
 __device__ inline double stirling_tail(double x) {
@@ -159,6 +172,27 @@ __device__ inline double dm_row_and_update(int k, const int64_t* __restrict__ c,
         }
         for (int j = 0; j < (int)tot; ++j) acc -= log(sb + (double)j);
         return acc;
+    }
+    if (plain && sb >= kStirling) {
+        const double half_ln_2pi = 0.9189385332046727;
+        const double ln_sb = log(sb);
+        double acc = 0.0;
+        for (int a = 0; a < k; ++a) {
+            const double b0 = ex ? b[a] : hn_beta[a];
+            const double bp = a == hs ? b0 + 1.0 : b0;
+            const double na = (double)(a == hs ? c[a] - 1 : c[a]);
+            const double v = bp + na;
+            if (na > 0.0) {
+                if (bp >= kStirling)
+                    acc += (v - 0.5) * log1p(na / bp) + na * log(bp / sb) + (stirling_tail(v) - stirling_tail(bp));
+                else if (v >= kStirling)
+                    acc += (v - 0.5) * log(v / sb) + (bp - 0.5) * ln_sb - bp + half_ln_2pi + stirling_tail(v) - lgamma_call(bp);
+                else
+                    acc += lgamma_call(v) - lgamma_call(bp) - na * (ln_sb - 1.0);
+            }
+            b[a] = b0 + (double)c[a];
+        }
+        return acc - ((sbn - 0.5) * log1p((double)tot / sb) + (stirling_tail(sbn) - stirling_tail(sb)));
     }
     LogBeta prior(sb), post(sbn);
     for (int a = 0; a < k; ++a) {
@@ -250,7 +284,9 @@ __global__ __launch_bounds__(kThreads) void sweep_level_kernel(int k, int d, int
         const double A = log1p(-g0) + L, B = log(g0) + S;
         const double t = A - B;       // logaddexp(A, B)
         mix = t == 0.0 ? A + 0.6931471805599453 : t > 0.0 ? A + log1p(exp(-t)) : B + log1p(exp(t));
-        gn = exp(B - mix);
+        // B - mix = -log1p(e^t).  Next to 1 (t < 0) that difference is known to an ulp of B only, which would cost 1 - g
+        // its digits; 1 / (1 + e^t) keeps them.
+        gn = t > 0.0 ? exp(B - mix) : 1.0 / (1.0 + exp(t));
     }
     g[s] = gn;
     exists[s] = 1;

@@ -105,6 +105,122 @@ def batch_update(x, k, D, t, hn_g, hn_beta_vec):
     return cnt
 
 
+# ---- the exact oracle: the same update in mpmath, for the tests that hold the kernels' floating-point formula to it ----------
+MP_DPS = 60
+
+
+def _mp():
+    import mpmath
+    mpmath.mp.dps = MP_DPS
+    return mpmath
+
+
+def _mp_row(b, n):
+    mp = _mp()
+    return [mp.mpf(float(v)) for v in b], [int(v) for v in n]
+
+
+def logdm_exact(b, n):
+    """lnDM(b, n) of one row (binary64 b taken as exact, integer n) as an mpf of MP_DPS digits."""
+    mp = _mp()
+    b, n = _mp_row(b, n)
+    return (mp.loggamma(mp.fsum(b)) - mp.loggamma(mp.fsum(b) + sum(n))
+            + mp.fsum(mp.loggamma(v + c) - mp.loggamma(v) for v, c in zip(b, n) if c != 0))
+
+
+def row_scale(b, n):
+    """The sizes of the terms lnDM adds: sum_a |lnG(b_a + n_a) - lnG(b_a)| + |lnG(sum b + sum n) - lnG(sum b)| (float)."""
+    mp = _mp()
+    b, n = _mp_row(b, n)
+    s = mp.fsum(abs(mp.loggamma(v + c) - mp.loggamma(v)) for v, c in zip(b, n) if c != 0)
+    return float(s + abs(mp.loggamma(mp.fsum(b) + sum(n)) - mp.loggamma(mp.fsum(b))))
+
+
+def head_key(head, k, d):
+    """Key at depth d of the head sample x[d] (its context is x[d-1], ..., x[0])."""
+    return sum(int(head[d - j]) * k ** (j - 1) for j in range(1, d + 1))
+
+
+def counts_from_deepest(cnt_deepest, head, k, D):
+    """[cnt_0, ..., cnt_D] from the deepest level's table and the first min(N, D) symbols: child sums plus the head samples."""
+    cnt = [None] * (D + 1)
+    cnt[D] = np.asarray(cnt_deepest, dtype=np.int64).reshape(k ** D, k)
+    for d in range(D - 1, -1, -1):
+        cnt[d] = cnt[d + 1].reshape(k, k ** d, k).sum(0)
+        if len(head) > d:
+            cnt[d][head_key(head, k, d), int(head[d])] += 1
+    return cnt
+
+
+def batch_update_exact(cnt_deepest, head, k, D, t, hn_g, hn_beta_vec):
+    """``batch_update`` in mpmath on the tables ``t`` (not modified), from the deepest level's count table and the head
+    (the first min(N, D) symbols of the sample; ``sweep`` takes the same two).  Returns a dict over all nodes:
+    ``g`` (object array of mpf: the exact new h_g; the old one where the node has no samples), ``B`` (float: the sum over
+    the node's subtree of row_scale + |logit g0| + |lead| of the touched nodes - the sizes of the terms that enter the
+    node's log-odds; logit g0 counts only for 0 < g0 < 1, where the logarithms are taken), ``beta``, ``exists`` (what the
+    update leaves), ``touched`` and ``logit`` (the exact new log-odds where 0 < g0 < 1, else None)."""
+    mp = _mp()
+    off = offsets(k, D)
+    head = [int(v) for v in head][:D]
+    cnt = counts_from_deepest(cnt_deepest, head, k, D)
+    hb = np.asarray(hn_beta_vec, dtype=float)
+    g = np.array([mp.mpf(float(v)) for v in t["g"]], dtype=object)
+    B = np.zeros(off[-1])
+    logit = np.full(off[-1], None, dtype=object)
+    beta, exists = t["beta"].copy(), t["exists"].copy()
+    touched = np.zeros(off[-1], bool)
+    lnw = None
+    for d in range(D, -1, -1):
+        nk = k ** d
+        lnw_here, hk = [mp.mpf(0)] * nk, head_key(head, k, d) if len(head) > d and d < D else -1
+        for s in range(nk):
+            i, c = off[d] + s, cnt[d][s]
+            if c.sum() == 0:
+                continue
+            touched[i] = True
+            ex = t["exists"][i] != 0
+            b0 = t["beta"][i] if ex else hb
+            g0 = mp.mpf(float(t["g"][i])) if ex else mp.mpf(0.0 if d == D else float(hn_g))
+            beta[i], exists[i] = b0 + c, 1
+            bp, n, lead = np.array(b0, dtype=float), c.copy(), mp.mpf(0)
+            if s == hk:
+                a = head[d]
+                lead = mp.log(mp.mpf(float(b0[a])) / mp.fsum(mp.mpf(float(v)) for v in b0))
+                bp[a] += 1.0            # exact: the tests' priors are multiples of 2^-10 far below 2^42
+                n[a] -= 1
+            L = logdm_exact(bp, n)
+            B[i] = row_scale(bp, n) + abs(float(lead))
+            if d == D:
+                lnw_here[s] = L
+                g[i] = mp.mpf(0) if not ex else g[i]
+                continue
+            ch = [s + c_ * nk for c_ in range(k)]
+            S = mp.fsum(lnw[j] for j in ch)
+            B[i] += sum(B[off[d + 1] + j] for j in ch)
+            if g0 <= 0:
+                mix, gn = L, mp.mpf(0)
+            elif g0 >= 1:
+                mix, gn = S, mp.mpf(1)
+            else:
+                a_, b_ = mp.log1p(-g0) + L, mp.log(g0) + S
+                m = max(a_, b_)
+                mix = m + mp.log(mp.exp(a_ - m) + mp.exp(b_ - m))
+                gn = mp.exp(b_ - mix)
+                logit[i] = b_ - a_
+                B[i] += abs(float(mp.log(g0) - mp.log1p(-g0)))
+            g[i], lnw_here[s] = gn, lead + mix
+        lnw = lnw_here
+    return dict(g=g, B=B, beta=beta, exists=exists, touched=touched, logit=logit)
+
+
+def g_bound(g_exact, B):
+    """The first-order image in g of a log-odds error of 64 eps B, plus half an ulp of g and the smallest normal number:
+    64 eps B g (1 - g) + 2^-52 g + 2^-1022 (an mpf)."""
+    mp = _mp()
+    eps = mp.mpf(2) ** -52
+    return 64 * eps * mp.mpf(float(B)) * g_exact * (1 - g_exact) + eps * g_exact + mp.mpf(2) ** -1022
+
+
 def subtree_pow(hn_g, k, D, depth):
     """The reference's price of a full subtree under a missing child of a node at ``depth`` (:757)."""
     m = (k ** (D - depth) - 1) / (k - 1) if k > 1 else float(D - depth)
@@ -298,14 +414,14 @@ def prior_tables(mod, case):
     return t
 
 
-def oracle_stages(mod, case, inp):
-    """after1 / after2 of the case by ``batch_update`` alone, for the oracle's own check."""
+def _stages(mod, case, inp, update):
+    """after1 / after2 of the case by ``update(x, t, hn_g, hn_beta_vec)``, which updates the tables ``t`` in place."""
     k, D = case["k"], case["D"]
     off = offsets(k, D)
     t = prior_tables(mod, case)
     g, b = case["h0_g"], np.arange(1, k + 1) / 2.0
     out = {}
-    batch_update(inp["x1"], k, D, t, g, b)
+    update(inp["x1"], t, g, b)
     out["after1"] = copy_tables(t)
     if case["hn2"] is not None:
         # set_hn_params(hn_g, hn_beta_vec): every existing node, then the all-zero context path of its calc_pred_dist
@@ -318,9 +434,26 @@ def oracle_stages(mod, case, inp):
             if not t["exists"][off[d]]:
                 t["exists"][off[d]], t["g"][off[d]], t["beta"][off[d]] = 1, g, b
     if len(inp["x2"]):
-        batch_update(inp["x2"], k, D, t, g, b)
+        update(inp["x2"], t, g, b)
         out["after2"] = copy_tables(t)
     return out
+
+
+def oracle_stages(mod, case, inp):
+    """after1 / after2 of the case by ``batch_update`` alone, for the oracle's own check."""
+    k, D = case["k"], case["D"]
+    return _stages(mod, case, inp, lambda x, t, g, b: batch_update(x, k, D, t, g, b))
+
+
+def exact_stages(mod, case, inp):
+    """``oracle_stages`` by ``batch_update_exact``: after1 / after2 h_g rounded to binary64 (the second update starts from
+    the rounded first, as every binary64 implementation does)."""
+    k, D = case["k"], case["D"]
+
+    def update(x, t, g, b):
+        r = batch_update_exact(level_counts(x, k, D)[D], x[:D], k, D, t, g, b)
+        t["g"], t["beta"], t["exists"] = np.array([float(v) for v in r["g"]]), r["beta"], r["exists"]
+    return _stages(mod, case, inp, update)
 
 
 def error_cases(mod, make=None):

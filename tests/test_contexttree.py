@@ -69,6 +69,42 @@ def test_oracle_matches_reference(name):
     assert np.array_equal(ml[in_tree], fx["map_leaf"][in_tree])
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_exact_oracle_matches_reference(name):
+    """``batch_update_exact`` (mpmath) against the reference's fixtures, to the bound the GPU's posterior is held to:
+    4 x ref_vs_batch + 64 eps in log-odds.  Pins the exact oracle of tests/test_gpu_contexttree_rows.py to the reference."""
+    case = orc.case_by_name(name)
+    fx, inp = load_golden(f"contexttree_{name}.npz"), orc.case_inputs(case)
+    stages = orc.exact_stages(_ct(), case, inp)
+    assert ("after2" in stages) == (case["n2"] > 0)
+    tol = 4 * float(fx["ref_vs_batch"]) + 64 * np.finfo(float).eps
+    for stage, t in stages.items():
+        ex = fx[f"{stage}_exists"]
+        assert np.array_equal(t["exists"], ex)
+        assert np.array_equal(t["beta"][ex != 0], fx[f"{stage}_beta"][ex != 0])
+        assert orc.log_odds_err(t["g"], fx[f"{stage}_g"], ex) <= tol
+
+
+def test_exact_logdm_matches_gammaln_on_benign_rows():
+    """Small priors and counts, where scipy's gammaln loses nothing: ``logdm`` is within 64 eps row_scale of
+    ``logdm_exact``; and two rows worked out by hand."""
+    rng, eps = np.random.default_rng(31), np.finfo(float).eps
+    for k in (2, 3, 4, 7):
+        for _ in range(25):
+            b = rng.choice([0.5, 1.0, 1.5, 2.5], k)
+            n = rng.integers(0, 40, k)
+            if n.sum() == 0:
+                continue
+            exact, scale = orc.logdm_exact(b, n), orc.row_scale(b, n)
+            assert scale >= abs(float(exact))
+            assert abs(float(orc.logdm(b, n.astype(float)) - exact)) <= 64 * eps * scale, (b, n)
+    # lnDM((1, 1), (1, 0)) = ln(1/2); lnDM((1, 1), (1, 1)) = ln(1 * 1 / (2 * 3)); row_scale of the second: 0 + 0 + ln 6
+    assert abs(float(orc.logdm_exact([1.0, 1.0], [1, 0])) + np.log(2.0)) < 4 * eps
+    assert abs(float(orc.logdm_exact([1.0, 1.0], [1, 1])) + np.log(6.0)) < 4 * eps
+    assert abs(orc.row_scale([1.0, 1.0], [1, 1]) - np.log(6.0)) < 4 * eps
+    assert abs(orc.row_scale([1.0, 1.0], [2, 0]) - 2 * np.log(2.0) - np.log(3.0)) < 4 * eps   # ln 2! + ln (3!/1!)
+
+
 def test_oracle_counts_drop_windows_with_bad_symbols():
     """Covers no product code: it pins ``deepest_counts``, the NumPy reference that the GPU bad-symbol test compares
     ctree_count with, to a case worked out by hand."""
