@@ -8,6 +8,33 @@ namespace gmmvb {
 
 // u [K][D][D] lower triangular (y = u d)  ->  per-component parameter image (layout: estep.h)
 //   [P][half][lane][2] tiles of u (zero padded to 16T) | [T][g][r] bias = -(u m) | zero pad to 1 KB
+// One component's image from its u, row stride ld: global memory (pack_params_kernel, ld = D) or the workgroup's LDS copy
+// of the lower triangle (pack_images_kernel, estep_i8.h), where only entries ii <= jj exist.  The bias is one thread per
+// row walking it with ii ascending: the order of the fma chain is part of the image's definition (bit-identical images
+// whatever the source of u).
+static __device__ __forceinline__ void pack_f64_image(const double* uk, int ld, const double* mk, int D, int T, int img_len,
+                                                      double* __restrict__ im) {
+    const int P = tri_pairs(T);
+    for (int e = threadIdx.x; e < P * 256; e += blockDim.x) {
+        const int p = e >> 8, h = (e >> 7) & 1, lane = (e >> 1) & 63, ee = e & 1;
+        int jt = 0;
+        while (tri_pairs(jt + 1) <= p) ++jt;
+        const int b = p - tri_pairs(jt);
+        const int jj = 16 * jt + (lane & 15), ii = 16 * b + 4 * (lane >> 4) + 2 * h + ee;
+        im[e] = (jj < D && ii < D && ii <= jj) ? uk[(int64_t)jj * ld + ii] : 0.0;
+    }
+    for (int jj = threadIdx.x; jj < 16 * T; jj += blockDim.x) {
+        double s = 0.0;
+        if (jj < D)
+            for (int ii = 0; ii <= jj; ++ii) s = fma(uk[(int64_t)jj * ld + ii], mk[ii], s);
+        const int jt = jj >> 4, w = jj & 15, g = w & 3, r = w >> 2;   // accumulator row = g + 4 r
+        im[P * 256 + (jt * 4 + g) * 4 + r] = -s;
+    }
+    for (int e = P * 256 + 16 * T + threadIdx.x; e < img_len; e += blockDim.x) im[e] = 0.0;
+}
+
+// The f64 image alone, u read from global memory: 128 < D <= 256, where a component's triangle does not fit in LDS (up to
+// D = 128 gmmvb_set_params packs every image in one launch, pack_images_kernel).
 // (also copies c -> cvec and, if asked, the pivot the int8 images are packed about: two device-to-device copies less per
 // parameter hand-over, each of which was a dispatch on the iteration's critical path)
 static __global__ void pack_params_kernel(const double* __restrict__ u, const double* __restrict__ m, int K, int D,
@@ -18,26 +45,7 @@ static __global__ void pack_params_kernel(const double* __restrict__ u, const do
     if (c_dst && threadIdx.x == 0) c_dst[k] = c_src[k];
     if (pivot_dst && k == 0)
         for (int f = threadIdx.x; f < D; f += blockDim.x) pivot_dst[f] = pivot_src[f];
-    const int P = tri_pairs(T);
-    const double* uk = u + (int64_t)k * D * D;
-    double* im = img + (int64_t)k * img_len;
-    for (int e = threadIdx.x; e < P * 256; e += blockDim.x) {
-        const int p = e >> 8, h = (e >> 7) & 1, lane = (e >> 1) & 63, ee = e & 1;
-        int jt = 0;
-        while (tri_pairs(jt + 1) <= p) ++jt;
-        const int b = p - tri_pairs(jt);
-        const int jj = 16 * jt + (lane & 15), ii = 16 * b + 4 * (lane >> 4) + 2 * h + ee;
-        im[e] = (jj < D && ii < D && ii <= jj) ? uk[(int64_t)jj * D + ii] : 0.0;
-    }
-    const double* mk = m + (int64_t)k * D;
-    for (int jj = threadIdx.x; jj < 16 * T; jj += blockDim.x) {
-        double s = 0.0;
-        if (jj < D)
-            for (int ii = 0; ii <= jj; ++ii) s = fma(uk[(int64_t)jj * D + ii], mk[ii], s);
-        const int jt = jj >> 4, w = jj & 15, g = w & 3, r = w >> 2;   // accumulator row = g + 4 r
-        im[P * 256 + (jt * 4 + g) * 4 + r] = -s;
-    }
-    for (int e = P * 256 + 16 * T + threadIdx.x; e < img_len; e += blockDim.x) im[e] = 0.0;
+    pack_f64_image(u + (int64_t)k * D * D, D, m + (int64_t)k * D, D, T, img_len, img + (int64_t)k * img_len);
 }
 
 // xc[n][f] = (double)x[n][f] - pivot[f] for f < D, 0 for D <= f < Dp (Dp = 16T): the M-step's operand,

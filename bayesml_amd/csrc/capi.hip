@@ -554,19 +554,23 @@ int gmmvb_set_params(gmmvb_workspace* ws, const double* c_dev, const double* m_d
     }
     // (c and the int8 images' pivot ride along: the digits are taken about the pivot in force now; the int8 kernels read that
     // copy, not ws->pivot)
-    hipLaunchKernelGGL(pack_params_kernel, dim3(ws->K), dim3(256), 0, st, u_dev, m_dev, ws->K, ws->D, ws->T,
-                       ws->img_len, ws->img, c_dev, ws->cvec, ws->pivot_i8 ? ws->pivot : nullptr, ws->pivot_i8);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(GMMVB_EHIP, "pack_params_kernel", e);
+    if (ws->wide) {
+        // 128 < D <= 256: a component's triangle does not fit in LDS, and there are no int8 images at that width
+        if (ws->pivot_i8) return fail(GMMVB_EUNSUPPORTED, "gmmvb_set_params: int8 images past D = 128");
+        hipLaunchKernelGGL(pack_params_kernel, dim3(ws->K), dim3(256), 0, st, u_dev, m_dev, ws->K, ws->D, ws->T, ws->img_len, ws->img,
+                           c_dev, ws->cvec, nullptr, nullptr);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(GMMVB_EHIP, "pack_params_kernel", e);
+    } else {
+        // one launch: the f64 image and every int8 image the workspace has (pack_images_kernel)
+        e = launch_pack_images(u_dev, m_dev, c_dev, ws->pivot, ws->K, ws->D, ws->T, ws->img_len, ws->img, ws->cvec, ws->pivot_i8,
+                               ws->pivot_i8 ? ws->img_i8 : nullptr, ws->pivot_i8 ? ws->img_i8b : nullptr, st);
+        if (e != hipSuccess) return fail(GMMVB_EHIP, "pack_images_kernel", e);
+        if (ws->pivot_i8) ws->img_gen = ws->pivot_gen;
+    }
     if (ws->tri) {
         e = launch_pack_tri16(u_dev, m_dev, ws->K, ws->D, ws->tri, st);
         if (e != hipSuccess) return fail(GMMVB_EHIP, "pack_tri16_kernel", e);
-    }
-    if (ws->pivot_i8) {
-        if (ws->img_i8) e = launch_pack_i8(u_dev, m_dev, ws->pivot_i8, ws->K, ws->D, ws->img_i8, 0, st);
-        if (e == hipSuccess && ws->img_i8b) e = launch_pack_i8(u_dev, m_dev, ws->pivot_i8, ws->K, ws->D, ws->img_i8b, 1, st);
-        if (e != hipSuccess) return fail(GMMVB_EHIP, "pack_params_i8_kernel", e);
-        ws->img_gen = ws->pivot_gen;
     }
     // The stateless sweep's table for these parameters (project.h), when a sweep can follow: regrouped rows, their tiles'
     // references, digit planes about the pivot in force, and a drift hint (the settled rows' own bound is still carried).

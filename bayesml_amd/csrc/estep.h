@@ -13,7 +13,7 @@
 //   exactly once.  The accumulator has the sample on the lane and the output row on (register,
 //   lane group), so ||y||^2 is a per-lane sum of squares plus two cross-group adds.
 //
-// Parameter image (written by pack_params_kernel, one per component, IMG doubles, 1 KB granules):
+// Parameter image (written by pack_images_kernel / pack_params_kernel, one per component, IMG doubles, 1 KB granules):
 //   [ P tile pairs ][ half h ][ lane 0..63 ][ 2 ]   element = U[16 jt + (lane & 15)][16 b + 4 (lane >> 4) + 2 h + e]
 //   [ T ][ g ][ r ]                                 bias    = -(U m)[16 jt + g + 4 r]
 // so that a wave reads its A fragments as two lane-linear 16-byte accesses (conflict-free in LDS,
@@ -291,7 +291,7 @@ static __global__ void pack_tri16_kernel(const double* __restrict__ u, const dou
             const int j = e - 136;
             double sacc = 0.0;
             if (j < D)
-                for (int i = 0; i <= j; ++i) sacc = fma(uk[(int64_t)j * D + i], mk[i], sacc);      // (as pack_params_kernel)
+                for (int i = 0; i <= j; ++i) sacc = fma(uk[(int64_t)j * D + i], mk[i], sacc);      // (as pack_f64_image)
             v = -sacc;
         }
         out[e] = v;

@@ -18,7 +18,7 @@
 // Output rows land on (register g, h): row = (g & 3) + 8 (g >> 2) + 4 h, so ||y||^2 is a per-lane sum plus one
 // cross-half add.
 //
-// Component image (bytes; 1-KB granules for the LDS-DMA, written by pack_params_i8_kernel):
+// Component image (bytes; 1-KB granules for the LDS-DMA, written by pack_i8_image):
 //   [ pair p = (jt, it <= jt) ][ digit a ][ lane ][ 16 ]   byte e of lane (r, h) = dU_a[32 jt + r][32 it + 16 h + e]
 //   [ jt ][ h ][ g ][ 2 ] doubles                         (2^ej, (U_k (m_k - pivot))_j) for row j = 32 jt + (g&3) + 8(g>>2) + 4h
 #pragma once
@@ -66,31 +66,26 @@ __device__ __forceinline__ void digits_of(double t, int (&d)[ND]) {
     }
 }
 
-// K-side: digits of u, row exponents, bias.  One block per component.
+// K-side: digits of u, row exponents, bias of one component, by one workgroup.  us: the workgroup's LDS copy of the lower
+// triangle of u_k, row stride ld (only entries i <= j of row j exist); dm = m_k - pivot (LDS).  row_*: [128] each, LDS.
+// The row scans are one thread per row with i ascending - the order of the fma chains is the one beta's error budget
+// below was derived for.
 template <int ND>
-__global__ void pack_params_i8_kernel(const double* __restrict__ u, const double* __restrict__ m,
-                                      const double* __restrict__ pivot, int K, int D, int T32, int img_bytes,
-                                      unsigned char* __restrict__ img) {
-    __shared__ double row_scale[128];   // 2^(6 - ej)  (0 for padding rows)
-    const int k = blockIdx.x;
+__device__ __forceinline__ void pack_i8_image(const double* us, int ld, const double* dm, int D, int T32, int img_bytes,
+                                              unsigned char* __restrict__ im, double* row_scale /* 2^(6 - ej), 0 for padding rows */,
+                                              double* row_max, double* row_beta, int* row_bad) {
     const int P = tri_pairs(T32);
-    const double* uk = u + (int64_t)k * D * D;
-    const double* mk = m + (int64_t)k * D;
-    unsigned char* im = img + (int64_t)k * img_bytes;
     double* consts = reinterpret_cast<double*>(im + P * ND * 1024);
-    __shared__ double row_max[128];
-    __shared__ double row_beta[128];
-    __shared__ int row_bad[128];
     for (int j = threadIdx.x; j < 32 * T32; j += blockDim.x) {
         double mx = 0.0, bias = 0.0, abias = 0.0;
         bool bad = false;
         if (j < D) {
             for (int i = 0; i <= j; ++i) {
-                const double v = uk[(int64_t)j * D + i];
+                const double v = us[j * ld + i];
                 bad |= !(fabs(v) <= 1.7976931348623157e308);
                 mx = fmax(mx, fabs(v));
-                bias = fma(v, mk[i] - pivot[i], bias);
-                abias = fma(fabs(v), fabs(mk[i] - pivot[i]), abias);
+                bias = fma(v, dm[i], bias);
+                abias = fma(fabs(v), fabs(dm[i]), abias);
             }
         }
         int e = 0;
@@ -144,7 +139,7 @@ __global__ void pack_params_i8_kernel(const double* __restrict__ u, const double
         while (tri_pairs(jt + 1) <= p) ++jt;
         const int it = p - tri_pairs(jt);
         const int jj = 32 * jt + (lane & 31), ii = 32 * it + 16 * (lane >> 5) + b;
-        const double v = (jj < D && ii <= jj) ? uk[(int64_t)jj * D + ii] * row_scale[jj] : 0.0;
+        const double v = (jj < D && ii <= jj) ? us[jj * ld + ii] * row_scale[jj] : 0.0;
         int d[ND];
         digits_of<ND>(v, d);
 #pragma unroll

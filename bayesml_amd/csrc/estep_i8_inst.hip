@@ -2,6 +2,8 @@
 // 3-digit bound pass of the pruned E-step.
 #include <cstdint>
 #include <cstdlib>
+#include <mutex>
+#include "aux_kernels.h"
 #include "estep_i8.h"
 #include "launch.h"
 
@@ -10,15 +12,75 @@ namespace gmmvb {
 int estep_i8_image_bytes(int D, int bound) { return i8_img_bytes(bound ? kBoundDigits : kDigits, i8_blocks(D)); }
 int estep_i8_rows_per_wg() { return 8 * 32; }
 
-hipError_t launch_pack_i8(const double* u, const double* m, const double* pivot, int K, int D, unsigned char* img,
-                          int bound, hipStream_t st) {
+// Every image of a parameter hand-over in one launch (gmmvb_set_params, D <= 128): blockIdx.x = component, blockIdx.y =
+// image kind - 0: the f64 image, c -> cvec and the pivot copy; then one per int8 image the workspace has (the 6-digit one
+// first).  Before: a launch per image, back to back at the head of every iteration, each walking the rows of u in global
+// memory with one thread per row (loads strided by D doubles across the lanes).  Now a workgroup stages the lower triangle
+// of u_k once with coalesced row reads - [D][ld] doubles, ld odd (129 at D = 128): a thread per row walks its row without
+// bank conflicts - and the row scans, the tile loop and the digit loop all read that copy.  The scans keep their order of
+// operations, so the images are the same bits as before.
+// The int8 workgroups take the pivot from its source: the copy in pivot_dst is being written by workgroup (0, 0) of the same
+// launch.
+constexpr int kPackThreads = 512;
+__global__ __launch_bounds__(kPackThreads) void pack_images_kernel(const double* __restrict__ u, const double* __restrict__ m,
+                                                                    const double* __restrict__ c_src, const double* __restrict__ pivot_src,
+                                                                    int K, int D, int T, int img_len, double* __restrict__ img,
+                                                                    double* __restrict__ c_dst, double* __restrict__ pivot_dst,
+                                                                    int T32, unsigned char* __restrict__ img6, int img6_bytes,
+                                                                    unsigned char* __restrict__ img3, int img3_bytes) {
+    extern __shared__ double us[];          // [D][ld] lower triangle of u_k | mv [D]
+    __shared__ double row_scale[128], row_max[128], row_beta[128];
+    __shared__ int row_bad[128];
+    const int k = blockIdx.x, kind = blockIdx.y;
+    const int ld = D | 1;
+    double* mv = us + D * ld;
+    const double* uk = u + (int64_t)k * D * D;
+    for (int e = threadIdx.x; e < D * D; e += kPackThreads) {
+        const int i = e / D, j = e - i * D;
+        if (j <= i) us[i * ld + j] = uk[e];
+    }
+    for (int i = threadIdx.x; i < D; i += kPackThreads) {
+        const double mi = m[(int64_t)k * D + i];
+        mv[i] = kind == 0 ? mi : mi - pivot_src[i];
+    }
+    __syncthreads();
+    if (kind == 0) {
+        if (threadIdx.x == 0) c_dst[k] = c_src[k];
+        if (pivot_dst && k == 0)
+            for (int f = threadIdx.x; f < D; f += kPackThreads) pivot_dst[f] = pivot_src[f];
+        pack_f64_image(us, ld, mv, D, T, img_len, img + (int64_t)k * img_len);
+    } else if (kind == 1 && img6) {
+        pack_i8_image<kDigits>(us, ld, mv, D, T32, img6_bytes, img6 + (int64_t)k * img6_bytes, row_scale, row_max, row_beta, row_bad);
+    } else {
+        pack_i8_image<kBoundDigits>(us, ld, mv, D, T32, img3_bytes, img3 + (int64_t)k * img3_bytes, row_scale, row_max, row_beta,
+                                    row_bad);
+    }
+}
+
+hipError_t launch_pack_images(const double* u, const double* m, const double* c_src, const double* pivot_src, int K, int D, int T,
+                              int img_len, double* img, double* cvec, double* pivot_dst, unsigned char* img6, unsigned char* img3,
+                              hipStream_t st) {
+    if (D > 128 || ((img6 || img3) && !pivot_dst)) return hipErrorInvalidValue;
+    // more than 64 KB of dynamic LDS has to be asked for, once per device
+    static std::mutex mu;
+    static bool asked[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (dev < 0 || dev >= 64 || !asked[dev]) {
+            e = hipFuncSetAttribute((const void*)pack_images_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((128 * 129 + 128) * sizeof(double)));
+            if (e != hipSuccess) return e;
+            if (dev >= 0 && dev < 64) asked[dev] = true;
+        }
+    }
     const int t32 = i8_blocks(D);
-    if (bound)
-        hipLaunchKernelGGL(pack_params_i8_kernel<kBoundDigits>, dim3(K), dim3(256), 0, st, u, m, pivot, K, D, t32,
-                           i8_img_bytes(kBoundDigits, t32), img);
-    else
-        hipLaunchKernelGGL(pack_params_i8_kernel<kDigits>, dim3(K), dim3(256), 0, st, u, m, pivot, K, D, t32,
-                           i8_img_bytes(kDigits, t32), img);
+    const size_t lds = ((size_t)D * (D | 1) + D) * sizeof(double);
+    const unsigned kinds = 1u + (img6 ? 1u : 0u) + (img3 ? 1u : 0u);
+    hipLaunchKernelGGL(pack_images_kernel, dim3(K, kinds), dim3(kPackThreads), lds, st, u, m, c_src, pivot_src, K, D, T, img_len, img,
+                       cvec, pivot_dst, t32, img6, i8_img_bytes(kDigits, t32), img3, i8_img_bytes(kBoundDigits, t32));
     return hipGetLastError();
 }
 

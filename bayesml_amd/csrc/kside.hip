@@ -11,6 +11,7 @@
 
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace gmmvb {
@@ -263,13 +264,32 @@ __global__ __launch_bounds__(1024) void chol_inv_blocked_kernel(const double* __
 // Per component and direction (blockIdx.y = 0: A = u_old u_new^-1 -> gamma = 1 / ||A||_2;  1: A = u_new u_old^-1 ->
 // big_gamma = ||A||_2):  G = A^T A, then `sq` times G <- G^2 / ||G^2||_F with the logarithms of the Frobenius norms
 // summed with weights 2^-i:  ||A||_2^2 = lambda_max(G) <= ||G^(2^s)||_F^(1/2^s), a rigorous upper bound, at most
-// D^(1/2^(s+1)) above the true norm.  The matrix lives in LDS ([128][129] doubles); a product is formed with every
-// thread holding an 8 x 8 block of the result in registers (rows ty + 16 a, columns tx + 16 b: conflict-free LDS
-// reads), then written back in place.  f64 FMA and f64 MFMA have the same peak on gfx950, so plain FMAs lose nothing.
+// D^(1/2^(s+1)) above the true norm.
 // Direction 2 does the same for E = u_new u_old^-1 - I -> enorm >= ||E||_2: once the components hardly move, 1 -/+ enorm
 // bounds the extreme singular values of u_new u_old^-1 far better than the two direct bounds (whose looseness factor
 // D^(1/2^(s+1)) applies to a norm close to 1; here it applies to a norm close to 0).  The caller takes the better of the two.
 // Block (k, 0) also computes delta[k] = || u_new (m_new - m_old) ||.
+//
+// Tile structure.  u and u^-1 are lower triangular (include/gmmvb.h), so every product has a triangle of 16 x 16 tiles
+// that is zero or a mirror image, and only the other one is computed (TR = PD / 16 tile rows; tile (tr, tc), tc <= tr):
+//   A = L R        lower triangular: contraction over the tiles tc .. tr only         TR (TR + 1)(TR + 2) / 6 tile products
+//   G = A^T A      symmetric: contraction over the tiles tr .. TR - 1 only             the same number
+//   G <- G^2 / f   symmetric in, symmetric out: the full contraction, one triangle     TR^2 (TR + 1) / 2
+// against TR^3 each before: 120, 120 and 288 instead of 512 at TR = 8, four v_mfma_f64_16x16x4_f64 per tile product.
+// The strict upper triangles of the inputs are never loaded.
+// LDS is one [PD][kDriftLd] matrix.  For A = L R it holds both operands: L in the lower triangle (diagonal included),
+// R transposed and one column to the right, R[i][j] at [j][i + 1] (the diagonal lands on the superdiagonal, the last
+// row of R in the spare column 128); a diagonal tile's 16 x 16 read takes in some of the other operand, which the lane
+// replaces with the zero that stands there.  A (direction 2: A - I) overwrites the lower tiles, its diagonal tiles with
+// the zeros the product gave above the diagonal; the strict upper tiles are not read again before G overwrites them.
+// G and its squares are stored in full: a wave writes an off-diagonal result tile a second time, transposed (the
+// [li][lg + 4 r] store is as conflict-free as the straight one), so every operand read is the plain one.  The Frobenius
+// norm is sum diag-tile^2 + 2 sum offdiag-tile^2.
+// Tile ownership: a wave computes one tile at a time (one accumulator, operands of the next contraction step fetched
+// while the four MFMAs of this one run) and keeps its results in registers until the barrier after which the matrix
+// may be overwritten.  The tiles differ in contraction length for A and G, so each product has its own deal
+// (DriftDeal: longest first, each to the wave with the least work so far): at TR = 8 every wave gets 15 of the 120 tile
+// products of A and of G, and 5 or 4 of the 36 tiles of a squaring - the waves w and w + 4 share a SIMD, which so gets 9.
 constexpr int kDriftLd = 129;
 
 template <int NW>
@@ -284,11 +304,108 @@ __device__ __forceinline__ double block_sum_waves(double v, double* red) {
     return t;
 }
 
-// PD = D rounded up to 32, 64 or 128: the products are PD x PD x PD (a D = 64 model does an eighth of the 128-wide work),
-// every thread holds a (PD / 16)^2 block of the result.
-// NW waves per workgroup: four, or eight for PD = 128 (round 4: with one wave per SIMD every MFMA group waited out the LDS
-// latency of its operands; two waves per SIMD overlap them, and a wave's accumulator block halves to one tile row:
-// 0.31 -> 0.21 ms per launch at the benchmark shape).
+enum DriftProduct { kDriftLR = 0, kDriftGram = 1, kDriftSquare = 2 };
+
+// contraction range (in tiles) of result tile (tr, tc), tc <= tr
+__host__ __device__ constexpr int drift_first(int mode, int tr, int tc) { return mode == kDriftLR ? tc : (mode == kDriftGram ? tr : 0); }
+__host__ __device__ constexpr int drift_last(int mode, int TR, int tr) { return mode == kDriftLR ? tr : TR - 1; }
+
+// Which lower tiles a wave computes: code[w] holds up to NS tiles, a byte each (tr << 4 | tc, 0xff = none), longest
+// contraction first.  Built at compile time; the kernel picks its word with NW selects on constants.
+template <int TR, int NW, int MODE>
+struct DriftDeal {
+    static constexpr int NT = TR * (TR + 1) / 2, NS = (NT + NW - 1) / NW;
+    unsigned long long code[NW];
+    constexpr DriftDeal() : code{} {
+        int tile[NT] = {}, cost[NT] = {};
+        int n = 0;
+        for (int tr = 0; tr < TR; ++tr)
+            for (int tc = 0; tc <= tr; ++tc, ++n) {
+                tile[n] = tr << 4 | tc;
+                cost[n] = drift_last(MODE, TR, tr) - drift_first(MODE, tr, tc) + 1;
+            }
+        for (int i = 1; i < NT; ++i)          // stable insertion sort, longest first
+            for (int j = i; j > 0 && cost[j - 1] < cost[j]; --j) {
+                const int t = tile[j], c = cost[j];
+                tile[j] = tile[j - 1], cost[j] = cost[j - 1];
+                tile[j - 1] = t, cost[j - 1] = c;
+            }
+        int load[NW] = {}, cnt[NW] = {};
+        for (int w = 0; w < NW; ++w) code[w] = ~0ull;
+        for (int i = 0; i < NT; ++i) {
+            int best = -1;
+            for (int w = 0; w < NW; ++w)
+                if (cnt[w] < NS && (best < 0 || load[w] < load[best])) best = w;
+            code[best] = (code[best] & ~(0xffull << (8 * cnt[best]))) | ((unsigned long long)tile[i] << (8 * cnt[best]));
+            load[best] += cost[i];
+            ++cnt[best];
+        }
+    }
+};
+
+// this wave's tiles of a product: byte s -> (tr, tc), or no tile
+template <int TR, int NW, int MODE>
+__device__ __forceinline__ unsigned long long drift_my_tiles(int wv) {
+    constexpr DriftDeal<TR, NW, MODE> deal;
+    unsigned long long c = ~0ull;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) c = wv == w ? deal.code[w] : c;
+    return c;
+}
+
+// One 16 x 16 result tile (tr, tc), tc <= tr, of the product MODE from the matrix in LDS, on one wave.
+// MFMA lane map (li = lane & 15, lg = lane >> 4): a = X[16 tr + li][p + lg], b = Y[p + lg][16 tc + li].
+//   kDriftLR      X = L (at [i][j]), Y = R (at [j][i + 1]); the diagonal tiles are masked to their triangle
+//   kDriftGram    X = A^T: X[row][p] = A[p][row], Y = A
+//   kDriftSquare  X = Y = G, stored in full
+template <int MODE, int TR>
+__device__ __forceinline__ d4 drift_tile(const double* sm, int tr, int tc, int li, int lg) {
+    const int p0 = drift_first(MODE, tr, tc), p1 = drift_last(MODE, TR, tr);
+    constexpr int as = MODE == kDriftGram ? kDriftLd : 1;          // stride of the contraction index in X and in Y
+    constexpr int bs = MODE == kDriftLR ? 1 : kDriftLd;
+    const double* ap = MODE == kDriftGram ? sm + lg * kDriftLd + 16 * tr + li : sm + (16 * tr + li) * kDriftLd + lg;
+    const double* bp = MODE == kDriftLR ? sm + (16 * tc + li) * kDriftLd + lg + 1 : sm + lg * kDriftLd + 16 * tc + li;
+    d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+    // Two operand sets in turn: the reads of one contraction step are issued before the four MFMAs of the step before it
+    // and stay there (left to itself the scheduler sinks them below those MFMAs to save registers, and the next step then
+    // waits out the LDS latency with the matrix pipe idle).
+    double a0[4], b0[4], a1[4], b1[4];
+    auto fetch = [&](double (&a)[4], double (&b)[4], int pt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a[q] = ap[(16 * pt + 4 * q) * as];
+            b[q] = bp[(16 * pt + 4 * q) * bs];
+        }
+    };
+    auto step = [&](double (&a)[4], double (&b)[4], int pt) {
+        if constexpr (MODE == kDriftLR) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (pt == tr) a[q] = 4 * q + lg <= li ? a[q] : 0.0;          // L's diagonal tile: column <= row
+                if (pt == tc) b[q] = 4 * q + lg >= li ? b[q] : 0.0;          // R's diagonal tile: row >= column
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc = mfma_f64(a[q], b[q], acc);
+    };
+    fetch(a0, b0, p0);
+#pragma unroll 1
+    for (int pt = p0; pt <= p1; pt += 2) {
+        fetch(a1, b1, pt + 1 <= p1 ? pt + 1 : p1);          // (past the end: the last step's operands again, unused)
+        __builtin_amdgcn_sched_barrier(0);
+        step(a0, b0, pt);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(a0, b0, pt + 2 <= p1 ? pt + 2 : p1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (pt + 1 <= p1) step(a1, b1, pt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return acc;
+}
+
+// PD = D rounded up to 32, 64 or 128: the products are over PD / 16 tile rows (a D = 64 model does an eighth of the
+// 128-wide work).  NW waves per workgroup: four, or eight for PD = 128 (two waves per SIMD overlap the LDS latency of
+// each other's operands).
 template <int PD, int NW>
 __global__ __launch_bounds__(64 * NW) void drift_kernel(const double* __restrict__ u_old, const double* __restrict__ uinv_old,
                                                     const double* __restrict__ m_old, const double* __restrict__ u_new,
@@ -322,7 +439,7 @@ __global__ __launch_bounds__(64 * NW) void drift_kernel(const double* __restrict
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const int i = lane + 64 * hh;
-                if (i < D) y = fma(u_new[base + (int64_t)r * D + i], dmv[hh], y);
+                if (i <= r) y = fma(u_new[base + (int64_t)r * D + i], dmv[hh], y);      // (the lower triangle: the rest is zero)
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) y += __shfl_xor(y, o);
@@ -331,99 +448,82 @@ __global__ __launch_bounds__(64 * NW) void drift_kernel(const double* __restrict
         const double t = block_sum_waves<NW>(part, red);
         if (tid == 0) delta[k] = sqrt(t) * (1.0 + 1e-9);
     }
-    // stage L (zero padded to PD x PD)
+    // stage the lower triangles: L[i][j] -> [i][j], R[i][j] -> [j][i + 1] (j <= i; rows and columns from D on are zero).
+    // Both row reads are coalesced; the transposed store walks a column of the odd-strided matrix: no bank conflict.
     for (int e = tid; e < PD * PD; e += 64 * NW) {
         const int i = e / PD, j = e % PD;
-        sm[i * kDriftLd + j] = (i < D && j < D) ? L[(int64_t)i * D + j] : 0.0;
+        if (j > i) continue;
+        const bool in = i < D;          // (then j < D too)
+        sm[i * kDriftLd + j] = in ? L[(int64_t)i * D + j] : 0.0;
+        sm[j * kDriftLd + i + 1] = in ? R[(int64_t)i * D + j] : 0.0;
     }
     __syncthreads();
-    // Every product runs on v_mfma_f64_16x16x4_f64 (round 3; before: 64 FMAs per thread and step with both operands from
-    // LDS, 35 us per 128^3 product where the pipe needs 14): the PD x PD result is TR x TR tiles of 16 x 16, wave w owns
-    // the tile rows w, w + 4, ... (TR / 4 of them, at least one) and all TR tile columns; lane (i = l & 15, g = l >> 4)
-    // supplies X[16 tr + i][p + g] and Y[p + g][16 tc + i] for the four steps p .. p + 3 of the contraction.
-    constexpr int TR = PD / 16, RW = TR >= NW ? TR / NW : 1;
-    const int lane = tid & 63, wv = tid >> 6, li = lane & 15, lg = lane >> 4;
-    const bool wave_on = wv * RW < TR;                 // (PD = 32: two of the four waves have a tile row)
-    d4 acc[RW][TR];
-    auto zero_acc = [&]() {
+    constexpr int TR = PD / 16;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    constexpr int NS = DriftDeal<TR, NW, kDriftLR>::NS;
+    d4 acc[NS];
+    auto product = [&](auto mode_tag, unsigned long long code) {
+        constexpr int MODE = decltype(mode_tag)::value;
 #pragma unroll
-        for (int a2 = 0; a2 < RW; ++a2)
-#pragma unroll
-            for (int b2 = 0; b2 < TR; ++b2) acc[a2][b2] = d4{0.0, 0.0, 0.0, 0.0};
-    };
-    // result tile (a2, b2), register r  <->  row 16 (RW wv + a2) + lg + 4 r, column 16 b2 + li
-    // A = L R : R straight from global memory / L2 (rows of R are contiguous in j: lanes li read neighbours)
-    zero_acc();
-    if (wave_on) {
-        for (int p = 0; p < PD; p += 4) {
-            double av[RW], bv[TR];
-#pragma unroll
-            for (int a2 = 0; a2 < RW; ++a2) av[a2] = sm[(16 * (RW * wv + a2) + li) * kDriftLd + p + lg];
-#pragma unroll
-            for (int b2 = 0; b2 < TR; ++b2) {
-                const int rr = p + lg, cc = 16 * b2 + li;
-                bv[b2] = (rr < D && cc < D) ? R[(int64_t)rr * D + cc] : 0.0;
-            }
-#pragma unroll
-            for (int a2 = 0; a2 < RW; ++a2)
-#pragma unroll
-                for (int b2 = 0; b2 < TR; ++b2) acc[a2][b2] = mfma_f64(av[a2], bv[b2], acc[a2][b2]);
+        for (int s = 0; s < NS; ++s) {
+            const int t = (int)(code >> (8 * s)) & 0xff;
+            acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+            if (t != 0xff) acc[s] = drift_tile<MODE, TR>(sm, t >> 4, t & 15, li, lg);
+            __builtin_amdgcn_sched_barrier(0);          // one tile at a time: interleaved, the tiles' operands fill the register file
         }
+    };
+    // A = L R
+    {
+        const unsigned long long code = drift_my_tiles<TR, NW, kDriftLR>(wv);
+        product(std::integral_constant<int, kDriftLR>{}, code);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int t = (int)(code >> (8 * s)) & 0xff;
+            if (t == 0xff) continue;
+            const int tr = t >> 4, tc = t & 15;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = 16 * tr + lg + 4 * r, j = 16 * tc + li;
+                sm[i * kDriftLd + j] = acc[s][r] - ((dir == 2 && i == j && i < D) ? 1.0 : 0.0);
+            }
+        }
+        __syncthreads();
     }
-    __syncthreads();
-    if (wave_on) {
-#pragma unroll
-        for (int a2 = 0; a2 < RW; ++a2)
-#pragma unroll
-            for (int b2 = 0; b2 < TR; ++b2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = 16 * (RW * wv + a2) + lg + 4 * r, j = 16 * b2 + li;
-                    sm[i * kDriftLd + j] = j < D ? acc[a2][b2][r] - ((dir == 2 && i == j && i < D) ? 1.0 : 0.0) : 0.0;
-                }
-    }
-    __syncthreads();
     // G = A^T A, then the squarings; every product is followed by its Frobenius norm
+    const unsigned long long code_gram = drift_my_tiles<TR, NW, kDriftGram>(wv), code_sq = drift_my_tiles<TR, NW, kDriftSquare>(wv);
     double log_lmax = 0.0, w = 1.0;
     for (int it = 0; it <= sq; ++it) {
-        zero_acc();
-        if (wave_on) {
-            for (int p = 0; p < PD; p += 4) {
-                double av[RW], bv[TR];
-                // it == 0: X = A^T, i.e. X[row][p] = A[p][row]
-#pragma unroll
-                for (int a2 = 0; a2 < RW; ++a2) {
-                    const int row = 16 * (RW * wv + a2) + li;
-                    av[a2] = it == 0 ? sm[(p + lg) * kDriftLd + row] : sm[row * kDriftLd + p + lg];
-                }
-#pragma unroll
-                for (int b2 = 0; b2 < TR; ++b2) bv[b2] = sm[(p + lg) * kDriftLd + 16 * b2 + li];
-#pragma unroll
-                for (int a2 = 0; a2 < RW; ++a2)
-#pragma unroll
-                    for (int b2 = 0; b2 < TR; ++b2) acc[a2][b2] = mfma_f64(av[a2], bv[b2], acc[a2][b2]);
-            }
-        }
+        const unsigned long long code = it == 0 ? code_gram : code_sq;
+        if (it == 0)
+            product(std::integral_constant<int, kDriftGram>{}, code);
+        else
+            product(std::integral_constant<int, kDriftSquare>{}, code);
         double ss = 0.0;
 #pragma unroll
-        for (int a2 = 0; a2 < RW; ++a2)
+        for (int s = 0; s < NS; ++s) {
+            const int t = (int)(code >> (8 * s)) & 0xff;
+            double st = 0.0;
 #pragma unroll
-            for (int b2 = 0; b2 < TR; ++b2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ss = fma(acc[a2][b2][r], acc[a2][b2][r], ss);
+            for (int r = 0; r < 4; ++r) st = fma(acc[s][r], acc[s][r], st);
+            ss += (t != 0xff && (t >> 4) != (t & 15)) ? 2.0 * st : st;          // (no tile: st = 0)
+        }
         double f = sqrt(block_sum_waves<NW>(ss, red));          // (the barrier inside also ends every read of the old matrix)
-        f = f > tiny ? f : tiny;                         // also NaN -> tiny: the NaNs then show up in log_lmax below
+        f = f < tiny ? tiny : f;                         // (a NaN stays: it reaches log_lmax and the read-out below)
         log_lmax += w * log(f);
         w *= 0.5;
         const double inv = 1.0 / f;
-        if (wave_on) {
 #pragma unroll
-            for (int a2 = 0; a2 < RW; ++a2)
+        for (int s = 0; s < NS; ++s) {
+            const int t = (int)(code >> (8 * s)) & 0xff;
+            if (t == 0xff) continue;
+            const int tr = t >> 4, tc = t & 15;
 #pragma unroll
-                for (int b2 = 0; b2 < TR; ++b2)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        sm[(16 * (RW * wv + a2) + lg + 4 * r) * kDriftLd + 16 * b2 + li] = acc[a2][b2][r] * inv;
+            for (int r = 0; r < 4; ++r) {
+                const double v = acc[s][r] * inv;
+                sm[(16 * tr + lg + 4 * r) * kDriftLd + 16 * tc + li] = v;
+                if (tr != tc) sm[(16 * tc + li) * kDriftLd + 16 * tr + lg + 4 * r] = v;          // the mirror image
+            }
         }
         __syncthreads();
     }
@@ -720,8 +820,12 @@ __global__ __launch_bounds__(NT) void kside_step_kernel(int K, int D, PriorView 
 }
 
 // scal = [p_x, p_z, p_pi, p_mu_lambda, q_z, q_pi, q_mu_lambda, vl, drift summary min_k (gamma_k - delta_k / 30)]
+// With a drift hint it first folds drift_kernel's third direction into the other two, gamma = max(gamma, 1 - e),
+// big = min(big, 1 + e), and writes them back (a K-thread launch of its own before: one dispatch less on the serial chain);
+// the summary is formed from the combined values.
 __global__ void kside_finish_kernel(int K, const double* __restrict__ partials, double ln_c_alpha,
-                                    const double* __restrict__ gamma, const double* __restrict__ delta,
+                                    double* __restrict__ gamma, const double* __restrict__ delta,
+                                    double* __restrict__ big, const double* __restrict__ enorm,
                                     double* __restrict__ scal) {
     // one workgroup of 64 (one thread's 9 K dependent loads were 0.1 ms at K = 256); thread 0 forms the lower bound from the
     // nine sums
@@ -751,7 +855,12 @@ __global__ void kside_finish_kernel(int K, const double* __restrict__ partials, 
         g = __builtin_huge_val();
         bool nan = false;
         for (int k = threadIdx.x; k < K; k += 64) {
-            const double v = gamma[k] - delta[k] / 30.0;
+            const double e = enorm[k] * (1.0 + 1e-9);
+            const double g2 = (1.0 - e) * (1.0 - 1e-9), b2 = (1.0 + e) * (1.0 + 1e-9);
+            const double gk = g2 > gamma[k] ? g2 : gamma[k];
+            gamma[k] = gk;
+            big[k] = b2 < big[k] ? b2 : big[k];
+            const double v = gk - delta[k] / 30.0;
             nan = nan || v != v;
             g = v < g ? v : g;
         }
@@ -780,16 +889,6 @@ __global__ void kside_finish_kernel(int K, const double* __restrict__ partials, 
     scal[6] = q_ml;
     scal[7] = p_x + p_z + p_pi + p_ml + q_z + q_pi + q_ml;
     scal[8] = g;
-}
-
-// gamma = max(gamma, 1 - e), big = min(big, 1 + e) (drift_kernel's third direction)
-__global__ void drift_combine_kernel(int K, double* __restrict__ gamma, double* __restrict__ big, const double* __restrict__ enorm) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= K) return;
-    const double e = enorm[k] * (1.0 + 1e-9);
-    const double g2 = (1.0 - e) * (1.0 - 1e-9), b2 = (1.0 + e) * (1.0 + 1e-9);
-    gamma[k] = g2 > gamma[k] ? g2 : gamma[k];
-    big[k] = b2 < big[k] ? b2 : big[k];
 }
 
 }  // namespace gmmvb
@@ -915,10 +1014,10 @@ extern "C" int gmmvb_kside_step(int K, int D, const gmmvb_prior_view* prior, con
         int rc = gmmvb_kside_drift(K, D, qa.u, qa.u_inv, qa.m, qb.u, qb.u_inv, qb.m, 8, 6, gamma_dev, delta_dev, big_gamma_dev, enorm,
                                    stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(drift_combine_kernel, dim3((K + 255) / 256), dim3(256), 0, st, K, gamma_dev, big_gamma_dev, enorm);
     }
     hipLaunchKernelGGL(kside_finish_kernel, dim3(1), dim3(64), 0, st, K, partials, pr.ln_c_alpha, want_drift ? gamma_dev : nullptr,
-                       want_drift ? delta_dev : nullptr, scal_dev);
+                       want_drift ? delta_dev : nullptr, want_drift ? big_gamma_dev : nullptr, want_drift ? enorm : nullptr,
+                       scal_dev);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(GMMVB_EHIP, "kside_finish_kernel launch", e);
     return GMMVB_OK;

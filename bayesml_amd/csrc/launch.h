@@ -91,8 +91,11 @@ struct EstepI8Args {
 // bound = 1: the 3-digit image / kernel of the pruned E-step's bound pass
 int estep_i8_image_bytes(int D, int bound);
 int estep_i8_rows_per_wg();
-hipError_t launch_pack_i8(const double* u, const double* m, const double* pivot, int K, int D, unsigned char* img,
-                          int bound, hipStream_t st);
+// every image of a parameter hand-over in one launch (D <= 128): the f64 image, c -> cvec, the pivot copy (pivot_dst, may be
+// null) and the int8 images given (img6: 6 digits, img3: the bound pass's 3 digits; either may be null)
+hipError_t launch_pack_images(const double* u, const double* m, const double* c_src, const double* pivot_src, int K, int D, int T,
+                              int img_len, double* img, double* cvec, double* pivot_dst, unsigned char* img6, unsigned char* img3,
+                              hipStream_t st);
 hipError_t launch_estep_i8(int x_is_f64, bool vec, int grid, hipStream_t st, const EstepI8Args& a, const char** name);
 // tb = output blocks (32 rows of y each) the bound pass evaluates, 1 .. ceil(D / 32)
 hipError_t launch_estep_i8_bound(int x_is_f64, bool vec, int tb, int grid, hipStream_t st, const EstepI8Args& a,
