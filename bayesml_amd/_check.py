@@ -210,3 +210,27 @@ def sample_kind(val):
         if val.dtype != torch.bool and not val.dtype.is_complex:
             return "i"
     return None
+
+
+def pos_ints(val, name, exc):
+    """_check.py:50-58 — integer scalar > 0, or integer ndarray whose values are all > 0."""
+    if _is_int(val) and val > 0:
+        return val
+    if _arr_kind(val) == "i" and np.all(val > 0):
+        return val
+    raise exc(name + " must be int or a numpy.ndarray whose dtype is int. Its values must be positive (not including 0).")
+
+
+def ints(val, name, exc):
+    """_check.py:60-66 — integer scalar or integer ndarray; no sign condition."""
+    if _is_int(val) or _arr_kind(val) == "i":
+        return val
+    raise exc(name + " must be int or a numpy.ndarray whose dtype is int.")
+
+
+def nonneg_float_vec(val, name, exc):
+    """_check.py:195-201 — 1-dimensional real ndarray without a negative entry."""
+    kind = _arr_kind(val)
+    if kind is not None and val.ndim == 1 and np.all(val >= 0):
+        return val.astype(float) if kind == "i" else val
+    raise exc(name + " must be a 1-dimensional numpy.ndarray. Its values must be non-negative (including 0).")

@@ -1,0 +1,132 @@
+/*
+ * mtree.h — C ABI of the meta-tree forest engine on the MI355X (gfx950), in libgmmvb.so beside gmmvb.h, regvb.h, expfam.h
+ * and ctree.h.
+ *
+ * The reference (bayesml/BayesML v0.3.1, bayesml/metatree/_metatree.py) updates a forest of meta-trees by boolean-mask
+ * recursion in Python, once per tree and once per node (:1729-1770), and predicts the same way (:3217-3310).  The batch
+ * form is: route every row through every tree (mtree_route), reduce the rows' y to per-node
+ * statistics without floating-point atomics (mtree_reduce), and sweep every tree bottom-up in one launch (mtree_sweep):
+ * children's statistics into the parent, the family's conjugate fold, its log marginal likelihood, and the two-way
+ * mixture that ctree.h's sweep applies.  mtree_predict folds the per-node predictive values along every row's path of
+ * every tree and mixes the trees.
+ *
+ * Conventions are ctree.h's: pointers named *_dev are DEVICE pointers owned by the caller, `stream` is a hipStream_t passed
+ * as void* (NULL = the null stream); calls only enqueue work, never allocate, never throw, never synchronise; the return
+ * value is a status code and mtree_last_error() gives a thread-local message.  Arguments are validated before anything
+ * touches the device, so bad arguments are reported without a GPU.
+ *
+ * The forest: flat node tables over all trees.  tree_off[b] is the first node of tree b (tree_off[n_trees] = n_nodes); within a
+ * tree the nodes are in breadth-first order, so a parent precedes its children and siblings are contiguous.  Per node:
+ * feat (the feature an inner node splits on, -1 for a leaf; features 0..dim_cont-1 are continuous, the rest categorical),
+ * child0 (table index of the first child), nchild, thr_off (a continuous inner node's nchild + 1 thresholds start at
+ * thr[thr_off]; the walk reads thr[thr_off + 1 .. thr_off + nchild - 1]) and depth (0 at a root).
+ *
+ * The walk of a row starts at the root.  A continuous node sends it to child 0 if x < thr[1], to child C-1 if
+ * thr[C-1] <= x, to child i if thr[i] <= x < thr[i+1]; a categorical node to child x.  A row that matches no child (NaN, a
+ * categorical value outside 0..C-1) stops at that node.  Every table index is range-checked on the device before use and a
+ * child index must be larger than its parent's and inside the tree, so a malformed table ends a walk instead of looping.
+ *
+ * Limits (the reference has none): MTREE_MAX_TREES trees, MTREE_MAX_NODES nodes per tree, MTREE_MAX_CHILDREN children per
+ * node, MTREE_MAX_DEGREE classes of the categorical sub-model, MTREE_MAX_DEPTH levels below a root.  Beyond them every entry
+ * point returns MTREE_EUNSUPPORTED.
+ */
+#ifndef MTREE_H
+#define MTREE_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MTREE_ABI_VERSION 1
+#define MTREE_MAX_TREES 1024
+#define MTREE_MAX_NODES 4096
+#define MTREE_MAX_CHILDREN 16
+#define MTREE_MAX_DEGREE 16
+#define MTREE_MAX_DEPTH 24
+#define MTREE_MAX_SLABS 64
+/* A tree whose statistics table (nodes x columns) has at most this many 8-byte slots (48 KiB) is reduced in a wave-private
+ * LDS table; a larger one in the wave's slab of global scratch. */
+#define MTREE_LDS_SLOTS 6144
+
+enum mtree_status { MTREE_OK = 0, MTREE_EINVAL = 1, MTREE_EUNSUPPORTED = 2, MTREE_EHIP = 3 };
+enum mtree_dtype { MTREE_U8 = 0, MTREE_I32 = 1, MTREE_I64 = 2, MTREE_F32 = 3, MTREE_F64 = 4 };
+enum mtree_family { MTREE_BERNOULLI = 0, MTREE_CATEGORICAL = 1, MTREE_POISSON = 2, MTREE_EXPONENTIAL = 3, MTREE_NORMAL = 4 };
+/* What mtree_predict writes per row: the mixed mean (one double), the mixed class probabilities (C doubles), their argmax
+ * (one int64), or the mixed predictive variance (one double; normal only). */
+enum mtree_pred { MTREE_PRED_MEAN = 0, MTREE_PRED_PROBA = 1, MTREE_PRED_CLASS = 2, MTREE_PRED_VAR = 3 };
+
+typedef struct mtree_forest {
+    int32_t n_trees, n_nodes, n_thr;        /* n_nodes, n_thr: entries of the node tables and of thr_dev, all trees */
+    int32_t max_tree_nodes, max_children;   /* the largest tree and the widest node (checked against the limits) */
+    int32_t max_depth;                      /* the deepest node's depth */
+    int32_t dim_cont, dim_cat;
+    const int32_t* tree_off_dev;            /* [n_trees + 1] */
+    const int32_t* feat_dev;                /* [n_nodes] each */
+    const int32_t* child0_dev;
+    const int32_t* nchild_dev;
+    const int32_t* thr_off_dev;
+    const int32_t* depth_dev;
+    const double* thr_dev;                  /* [n_thr] (may be NULL when n_thr = 0) */
+} mtree_forest;
+
+int mtree_abi_version(void);
+const char* mtree_last_error(void);
+
+/* Columns of the family's statistics: n_int int64 columns [ n | ... ] and n_real binary64 columns per node, and the length
+ * n_post of its posterior vector:
+ *   bernoulli    int [n, sum y]            real -                         post [alpha, beta]
+ *   categorical  int [n, c_0..c_{deg-1}]   real -                         post [alpha_0..alpha_{deg-1}]
+ *   poisson      int [n, sum y]            real [sum ln y!]               post [alpha, beta, sum ln y!]
+ *   exponential  int [n]                   real [sum y]                   post [alpha, beta]
+ *   normal       int [n]                   real [sum (y - pivot), SS]     post [m, kappa, alpha, beta, n]
+ * Returns 0, or MTREE_EINVAL / MTREE_EUNSUPPORTED for an unknown family or a degree outside 1..MTREE_MAX_DEGREE. */
+int mtree_stat_cols(int family, int degree, int* n_int, int* n_real, int* n_post);
+/* 8-byte slots of scratch for mtree_reduce and mtree_sweep with n_slabs slabs (one buffer serves both); -1 on bad arguments. */
+int64_t mtree_work_len(int32_t n_nodes, int family, int degree, int n_slabs);
+
+/* stop_dev[b * n + i] = the node where row i's walk in tree b stops.  xc_dev: [n][dim_cont] of xc_dtype (F32 or F64), xk_dev:
+ * [n][dim_cat] of xk_dtype (U8, I32 or I64), row-major, read where they lie (NULL where the dimension is 0).  cat_card_dev:
+ * [dim_cat] int32, the number of values of every categorical feature; bad_dev[0] is set to the number of categorical entries
+ * outside 0..cat_card-1 (they are never used as an index).  path_dev: NULL, or int32 [n_trees][n][max_depth + 1]: the nodes of
+ * the walk, root first, padded with -1. */
+int mtree_route(const mtree_forest* f, int xc_dtype, const void* xc_dev, int xk_dtype, const void* xk_dev,
+                const int32_t* cat_card_dev, int64_t n, int32_t* stop_dev, int32_t* path_dev, int64_t* bad_dev, void* stream);
+
+/* Per (tree, stop node), the statistics of the y of the rows that stop there, into stat_int_dev[n_nodes][n_int] and
+ * stat_real_dev[n_nodes][n_real] (overwritten).  y_dev: n values, int64 for bernoulli / categorical / poisson, binary64 for
+ * exponential / normal; a value outside the family's support is left out of every column but n.  pivot_dev: NULL or one
+ * binary64 that is subtracted from every y of the normal family before it is summed.  Integer columns are integer atomics
+ * (exact, order-free).  Real columns use no floating-point atomics and are bit-reproducible: a wave owns a contiguous slab
+ * of rows of one tree and a table only it writes, adds the lanes that share a node in fixed lane order, and the slabs are
+ * added in slab order.  For normal a second pass sums (y - mean of the stop node)^2. */
+int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev,
+                 const double* pivot_dev, int64_t n, int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev,
+                 void* stream);
+
+/* One launch, a workgroup per tree, depth by depth from the deepest to the root.  In place: the statistics become subtree
+ * totals (children added in child order; normal merges SS = sum_c [SS_c + n_c (mean_c - mean)^2]); a node with n = 0 is left
+ * bit-identical and its parent takes 0.0 for it; every other node gets its posterior folded (post_dev[n_nodes][n_post]),
+ * lml_dev[node] = the family's log marginal likelihood of the folded posterior against h0_dev[n_post], and an inner node
+ * g <- exp(t1 - L), t1 = ln g + sum of the children's L, L = logaddexp(ln(1 - g) + lml, t1); g = 0 and g = 1 are fixed
+ * points.  lcm_dev[c] = the L (0.0 for an empty child) that the visited parent of node c took for it, the reference's
+ * log_children_marginal_likelihood.  lnp_dev[b] += L of the root. */
+int mtree_sweep(const mtree_forest* f, int family, int degree, int64_t* stat_int_dev, double* stat_real_dev,
+                const double* pivot_dev, const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev,
+                double* lcm_dev, double* lnp_dev, void* work_dev, void* stream);
+
+/* values_dev[n_nodes][C] is filled from the posteriors (per node, once per call), then every row's walk in every tree is
+ * folded bottom-up, value(v) = (1 - g_v) p_v + g_v value(child), p_stop at the node where the walk stops, and the trees are
+ * mixed with prob_dev[n_trees].  C = 1 for MEAN and VAR (VAR uses two tables of C = 1: values_dev holds 2 n_nodes doubles),
+ * 2 for bernoulli and `degree` for categorical with PROBA / CLASS.  out_dev: binary64 [n] (MEAN, VAR), [n][C] (PROBA) or
+ * int64 [n] (CLASS).  A family that has no such read-out (MEAN on a classifier, PROBA / CLASS on a regressor, VAR on anything
+ * but normal) is MTREE_EINVAL. */
+int mtree_predict(const mtree_forest* f, int family, int degree, int mode, int xc_dtype, const void* xc_dev, int xk_dtype,
+                  const void* xk_dev, int64_t n, const double* post_dev, const double* g_dev, const double* prob_dev,
+                  double* values_dev, void* out_dev, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MTREE_H */

@@ -1,0 +1,364 @@
+"""metatree without a GPU: the exact oracle against the reference's fixtures, every LearnModel / GenModel method through the
+NumPy stand-in engine (tests/fake_metatree_engine.py) against the fixtures and the recorded boundary outcomes, and the
+mtree_* argument checks of the library."""
+import ctypes
+import json
+import os
+import pickle
+import warnings
+
+import numpy as np
+import pytest
+
+import fake_metatree_engine as fk
+import metatree_oracle as orc
+from conftest import GOLDEN, load_golden
+
+EPS = np.finfo(float).eps
+NAMES = [c["name"] for c in orc.CASES]
+CASE = {c["name"]: c for c in orc.CASES}
+
+
+def _subs():
+    from bayesml_amd import bernoulli, categorical, exponential, normal, poisson
+    return dict(bernoulli=bernoulli, categorical=categorical, poisson=poisson, exponential=exponential, normal=normal)
+
+
+@pytest.fixture()
+def mt():
+    from bayesml_amd import metatree
+    fk.use_cpu(metatree.LearnModel)
+    yield metatree
+    metatree.LearnModel._mtree_pass_factory = None
+
+
+def test_package_exports_metatree():
+    import bayesml_amd
+    for name in ("metatree", "linearregression", "autoregressive"):
+        assert name in bayesml_amd.__all__ and hasattr(bayesml_amd, name)
+    assert {"GenModel", "LearnModel"} <= set(bayesml_amd.metatree.__all__)
+    assert bayesml_amd.metatree.LearnModel._mtree_pass_factory is None
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_fixture_inputs_follow_the_recipe(name):
+    fx, inp = load_golden(f"metatree_{name}.npz"), orc.case_inputs(CASE[name])
+    for k, v in inp.items():
+        assert np.array_equal(fx[k], v), k
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_oracle_against_fixtures(name):
+    """The exact batch form from the stored forest and prior state: within the recorded ref_vs_batch of the reference at
+    both stages (counts and integer columns exactly), and the oracle's read-outs on that state within theirs."""
+    fx, case = load_golden(f"metatree_{name}.npz"), CASE[name]
+    fam, dc = orc.FAMILY[case["sub"]], case["consts"]["c_dim_continuous"]
+    degree = case.get("sub_constants", {}).get("c_degree", 0)
+    h0 = orc.post_of(fam, _subs()[case["sub"]].LearnModel(**case.get("sub_constants", {})))
+    flat = {k: fx[k] for k in orc.STRUCT}
+    n = len(flat["feat"])
+    st = dict(g=fx["init_g"], post=np.tile(h0, (n, 1)), lml=np.full(n, np.nan), lcm=np.zeros(n), prob=fx["init_prob"])
+    for stage, tag in (("after1", "1"), ("after2", "2")):
+        st, _ = orc.batch_update(flat, st, fam, degree, h0, dc, fx["xc" + tag], fx["xk" + tag], fx["y" + tag])
+        errs = orc.state_errs({k: fx[f"{stage}_{k}"] for k in orc.STATE}, st)
+        for k, e in errs.items():
+            assert e <= float(fx["ref_vs_batch_" + k]), (stage, k, e)
+        if fam in (orc.BERNOULLI, orc.CATEGORICAL):
+            assert np.array_equal(st["post"], fx[f"{stage}_post"])
+        assert orc.fixed_points_kept(fx["init_g"], st["g"])
+    for k, v in orc.oracle_readouts(flat, st, case, {k: fx[k] for k in ("xcp", "xkp", "yp")}).items():
+        assert orc.rel_err(fx[k], v) <= float(fx["ref_vs_batch_" + k]), k
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_learnmodel_against_fixtures(mt, name):
+    """Every stage and read-out of the case through LearnModel on the stand-in, replayed from the stored forest."""
+    fx, case = load_golden(f"metatree_{name}.npz"), CASE[name]
+    forest = ({k: fx[k] for k in orc.STRUCT}, fx["init_g"], fx["init_prob"])
+    out = orc.drive(mt, _subs(), case, orc.case_inputs(case), forest=forest)
+    tol = {k: 4 * float(fx["ref_vs_batch_" + k]) + 64 * EPS for k in ("g", "post", "lml", "prob")}
+    for k in orc.STRUCT:
+        assert np.array_equal(out[k], fx[k]), k
+    for stage in ("after1", "after2"):
+        errs = orc.state_errs({k: out[f"{stage}_{k}"] for k in orc.STATE}, {k: fx[f"{stage}_{k}"] for k in orc.STATE})
+        for k, e in errs.items():
+            assert e <= tol[k], (stage, k, e)
+        assert orc.rel_err(out[f"{stage}_lcm"], fx[f"{stage}_lcm"]) <= tol["lml"]
+    read = orc.readout_tols(fx)
+    for k in orc.READOUTS:
+        if k in fx and np.asarray(fx[k]).dtype.kind == "f":
+            assert orc.rel_err(out[k], fx[k]) <= read[k], k
+    if out["predict"].dtype.kind != "f":
+        top = np.sort(fx["predict_proba"], axis=1)
+        clear = top[:, -1] - top[:, -2] > 2 * read["predict_proba"]
+        assert clear.mean() > 0.9 and np.array_equal(out["predict"][clear], fx["predict"][clear])
+    assert int(out["map_index"]) == int(fx["map_index"]) and np.array_equal(out["map_leaf"], fx["map_leaf"])
+
+
+def test_boundary_outcomes(mt):
+    with open(os.path.join(GOLDEN, "metatree_errors.json")) as f:
+        want = json.load(f)
+    got = {name: orc.outcome(fn) for name, fn in orc.error_cases(mt, _subs()).items()}
+    assert got == want
+
+
+def test_bad_categorical_changes_nothing(mt):
+    from bayesml_amd import DataFormatError
+    case = CASE["threeway"]
+    inp = orc.case_inputs(case)
+    flat, g = orc._hand_forest()
+    m = mt.LearnModel(SubModel=_subs()["bernoulli"], **orc._HAND)
+    m.set_hn_params(hn_metatree_list=orc.nodes_from_flat(mt, flat, g, _subs()["bernoulli"].LearnModel))
+    m.update_posterior(inp["xc1"], inp["xk1"], inp["y1"], alg_type="given_MT")
+    before = {k: np.array(v) for k, v in m._hn_forest().state.items()}
+    import torch
+    bad = torch.from_numpy(inp["xk2"].copy())          # (a tensor: the host pre-check leaves its values to the engine)
+    bad[3, 0] = 3
+    with pytest.raises(DataFormatError, match=r"x_categorical\[:,0\].max\(\) must smaller than"):
+        m.update_posterior(torch.from_numpy(inp["xc2"]), bad, torch.from_numpy(inp["y2"]), alg_type="given_MT")
+    for k, v in m._hn_forest().state.items():
+        assert np.array_equal(v, before[k], equal_nan=True), k
+
+
+def test_pred_and_update_get_p_params_and_mtrf_refusal(mt):
+    """pred_and_update = the prediction from the state before, then a 'given_MT' update on the same rows (every loss the
+    family has); get_p_params is None as in the reference; a sample MTRF refuses leaves the posterior forest as it was,
+    whatever holds the sample."""
+    import torch
+    from bayesml_amd import CriteriaError, DataFormatError
+    inp = orc.case_inputs(CASE["threeway"])
+    flat, g = orc._hand_forest()
+
+    def model(sub_name, **kw):
+        sub = _subs()[sub_name]
+        m = mt.LearnModel(SubModel=sub, **{**orc._HAND, **kw})
+        return m.set_hn_params(hn_metatree_list=orc.nodes_from_flat(mt, flat, g, sub.LearnModel))
+
+    for loss, read in (("KL", lambda m: m.predict_proba(inp["xc2"], inp["xk2"])), ("0-1", lambda m: m.predict(inp["xc2"], inp["xk2"])),
+                       (None, lambda m: m.predict(inp["xc2"], inp["xk2"]))):
+        a, b = model("bernoulli"), model("bernoulli")
+        for m in (a, b):
+            m.update_posterior(inp["xc1"], inp["xk1"], inp["y1"], alg_type="given_MT")
+        want = read(b)
+        b.update_posterior(inp["xc2"], inp["xk2"], inp["y2"], alg_type="given_MT")
+        assert np.array_equal(a.pred_and_update(inp["xc2"], inp["xk2"], inp["y2"], loss=loss), want)
+        for k in orc.STATE:
+            assert np.array_equal(a._hn_forest().state[k], b._hn_forest().state[k], equal_nan=True), (loss, k)
+    with pytest.raises(CriteriaError):
+        a.pred_and_update(inp["xc2"], inp["xk2"], inp["y2"], loss="squared")
+    assert a.get_p_params() is None
+    # MTRF on a binary model: the bad value is found before scikit-learn runs and before the forest is replaced
+    m = mt.LearnModel(2, 1)
+    x, k, y = inp["xc1"], inp["xk1"] % 2, inp["y1"]
+    for bad in (np.where(np.arange(len(k))[:, None] == 5, 2, k), torch.from_numpy(np.where(np.arange(len(k))[:, None] == 5, 2, k))):
+        with pytest.raises(DataFormatError, match="must smaller than"):
+            m.update_posterior(x, bad, y, alg_type="MTRF", n_estimators=2)
+        assert m._hn is None and m.hn_metatree_list == []
+    with pytest.raises(DataFormatError):
+        a.calc_pred_dist(inp["xcp"], torch.from_numpy(inp["xkp"]) - 1)
+
+
+def test_genmodel_save_sample(mt, tmp_path):
+    g = mt.GenModel(2, 1, seed=5).gen_params()
+    g.save_sample(str(tmp_path / "s"), 7)
+    twin = mt.GenModel(2, 1, seed=5).gen_params()
+    with np.load(tmp_path / "s.npz") as z:
+        for got, want in zip((z["x_continuous"], z["x_categorical"], z["y"]), twin.gen_sample(7)):
+            assert np.array_equal(got, want)
+        assert z["x_continuous"].shape == (7, 2) and z["x_categorical"].shape == (7, 1) and z["y"].shape == (7,)
+
+
+def test_out_of_scope_items_name_themselves(mt):
+    from bayesml_amd import linearregression
+    from bayesml_amd._engine import EngineLimitError
+    with pytest.raises(EngineLimitError, match="linearregression"):
+        mt.LearnModel(2, 0, SubModel=linearregression)
+    with pytest.raises(EngineLimitError, match="linearregression"):
+        mt.GenModel(2, 0, SubModel=linearregression)
+    m = mt.LearnModel(2, 0)
+    x, y = np.zeros((4, 2)), np.zeros(4, dtype=int)
+    for alg in ("MTMCMC", "REMTMCMC"):
+        with pytest.raises(NotImplementedError, match=alg):
+            m.update_posterior(x, None, y, alg_type=alg)
+    for call in (m.visualize_posterior, lambda: m.estimate_params(visualize=True), mt.GenModel(2, 0).visualize_model):
+        with pytest.raises(NotImplementedError, match="plotting"):
+            call()
+    with pytest.raises(EngineLimitError, match="bayesml itself has no such limit"):
+        mt.LearnModel(1, 1, c_num_children_vec=np.array([2, 17]))
+
+
+def test_mtrf_equals_given_mt_on_its_forest(mt):
+    """MTRF end to end: the forest scikit-learn grows is copied (leaves h_g = 0, thresholds between the range ends,
+    k_candidates shrinking under c_num_assignment_vec), merged and updated; the same forest handed back with 'given_MT'
+    gives the same posterior."""
+    pytest.importorskip("sklearn")
+    case = dict(CASE["normal"], consts=dict(CASE["normal"]["consts"], c_num_assignment_vec=np.array([4, -1, -1, 4, -1])))
+    inp, sub = orc.case_inputs(case), _subs()["normal"]
+    a = mt.LearnModel(SubModel=sub, **case["consts"])
+    a.fit(inp["xc1"][:500], inp["xk1"][:500], inp["y1"][:500], n_estimators=6, random_state=1)
+    fa, sa, _ = orc.flatten(a.hn_metatree_list, a.hn_metatree_prob_vec, orc.NORMAL)
+    assert len(fa["tree_off"]) - 1 <= 6 and fa["depth"].max() <= 4 and np.all(sa["g"][fa["feat"] < 0] == 0.0)
+    for root in a.hn_metatree_list:                    # a feature with a bounded number of assignments is used up by its use
+        stack = [root]
+        while stack:
+            node = stack.pop()
+            assert node.leaf or node.k in node.k_candidates
+            if not node.leaf:
+                assert node.k >= 3 or node.ranges[node.k, 0] <= node.thresholds[1] <= node.ranges[node.k, 1]
+                if node.k in (0, 3):
+                    assert all(c.k_candidates.count(node.k) == node.k_candidates.count(node.k) - 1 for c in node.children)
+                stack.extend(node.children)
+    b = mt.LearnModel(SubModel=sub, **case["consts"])
+    trees = a._mtrf(inp["xc1"][:500], inp["xk1"][:500], inp["y1"][:500], n_estimators=6, random_state=1)
+    b._set_hn(trees)
+    b.update_posterior(inp["xc1"][:500], inp["xk1"][:500], inp["y1"][:500], alg_type="given_MT")
+    _, sb, _ = orc.flatten(b.hn_metatree_list, b.hn_metatree_prob_vec, orc.NORMAL)
+    for k in orc.STATE:
+        assert np.array_equal(sa[k], sb[k], equal_nan=True), k
+
+
+def test_forest_round_trips(mt):
+    """A _Node forest through the setters and getters, h0 -> hn, overwrite_h0_params, and pickling."""
+    sub = _subs()["poisson"]
+    flat, g = orc._hand_forest()
+    m = mt.LearnModel(SubModel=sub, h0_g=0.25, sub_h0_params={"h0_alpha": 2.0}, **orc._HAND)
+    assert m.hn_metatree_list == [] and m.hn_metatree_prob_vec is None
+    m.set_h0_params(h0_metatree_list=orc.nodes_from_flat(mt, flat, g, sub.LearnModel),
+                    h0_metatree_prob_vec=np.array([0.25, 0.75]))
+    for which in ("h0", "hn"):
+        params = getattr(m, f"get_{which}_params")()
+        assert list(params) == [f"{which}_k_weight_vec", f"{which}_g", f"sub_{which}_params", f"{which}_metatree_list",
+                                f"{which}_metatree_prob_vec"]
+        f2, s2, _ = orc.flatten(params[f"{which}_metatree_list"], params[f"{which}_metatree_prob_vec"], orc.POISSON)
+        for k in orc.STRUCT:
+            assert np.array_equal(f2[k], flat[k]), (which, k)
+        assert np.array_equal(s2["g"], g) and np.array_equal(s2["prob"], [0.25, 0.75])
+        assert np.all(np.isnan(s2["lml"]))
+    root = m.hn_metatree_list[0]
+    assert root.k_candidates == [0, 1, 2] and root.children[1].k_candidates == [1, 2]       # c_num_assignment_vec = [1, -1, -1]
+    assert np.array_equal(root.children[1].ranges, [[-1.0, 1.0], [-3.0, 3.0]]) and root.log_marginal_likelihood is None
+    inp = orc.case_inputs(CASE["threeway_n1"])
+    m.set_hn_params(hn_g=0.6)
+    assert m.hn_metatree_list[0].h_g == 0.6 and m.hn_metatree_list[0].children[1].children[0].h_g == 0.0
+    m.update_posterior(inp["xc1"], inp["xk1"], inp["y1"], alg_type="given_MT")
+    m2 = pickle.loads(pickle.dumps(m))
+    for k, v in m._hn_forest().state.items():
+        assert np.array_equal(v, m2._hn_forest().state[k], equal_nan=True), k
+    assert np.array_equal(m.predict(inp["xcp"], inp["xkp"]), m2.predict(inp["xcp"], inp["xkp"]))
+    m.overwrite_h0_params()
+    # (ref:1301-1306: the copy reads a LearnModel node's h0, so structure and h_g come over and the sub-models' prior stays)
+    assert m.h0_metatree_list[0].sub_model.h0_alpha == 2.0 and m.h0_metatree_list[0].h_g == m2.hn_metatree_list[0].h_g
+    with pytest.raises(Exception, match="must be a list"):
+        m.set_hn_params(hn_metatree_list=root)
+    with pytest.raises(Exception, match="must be the same"):
+        m.set_hn_params(hn_metatree_prob_vec=np.array([1.0]))
+
+
+def test_genmodel_follows_the_reference_draws(mt):
+    """gen_params and gen_sample under a seed: structure and integers exactly, floats to the last digit but one (the
+    expfam_*_gen fixtures' rule: 4 eps relative)."""
+    fx = load_golden("metatree_gen.npz")
+    subs = _subs()
+    for name, sub, kw in (("bern", subs["bernoulli"], {}), ("norm", subs["normal"], dict(threshold_type="random"))):
+        m = mt.GenModel(2, 1, c_max_depth=3, c_num_children_vec=np.array([2, 3, 2]), SubModel=sub, h_g=0.75, seed=7)
+        m.gen_params(**kw)
+        flat = orc.flatten_gen(m.root)
+        for k in ("feat", "nchild", "depth"):
+            assert np.array_equal(flat[k], fx[f"{name}_{k}"]), (name, k)
+        for k in ("thr", "g", "params"):
+            assert np.allclose(flat[k], fx[f"{name}_{k}"], rtol=4 * EPS, atol=0, equal_nan=True), (name, k)
+        xc, xk, y = m.gen_sample(40)
+        assert np.array_equal(xk, fx[f"{name}_xk"]) and np.allclose(xc, fx[f"{name}_xc"], rtol=4 * EPS, atol=0)
+        if y.dtype.kind == "i":
+            assert np.array_equal(y, fx[f"{name}_y"])
+        else:
+            assert np.allclose(y, fx[f"{name}_y"], rtol=4 * EPS, atol=0)
+    g = mt.GenModel(2, 1, seed=3)
+    assert list(g.get_constants()) == ["c_dim_continuous", "c_dim_categorical", "c_num_children_vec", "c_max_depth",
+                                       "c_num_assignment_vec", "c_ranges", "sub_constants"]
+    assert list(g.get_h_params()) == ["h_k_weight_vec", "h_g", "sub_h_params", "h_metatree_list", "h_metatree_prob_vec"]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        g.gen_params(feature_fix=True).gen_params(feature_fix=True, tree_fix=True)
+    h = mt.GenModel(2, 1, seed=4).set_params(g.get_params()["root"])
+    assert orc.flatten_gen(h.root)["feat"].tolist() == orc.flatten_gen(g.root)["feat"].tolist()
+    x_c, x_k, y = h.gen_sample(x_continuous=np.zeros((5, 2)))
+    assert x_k.shape == (5, 1) and y.shape == (5,)
+
+
+# ---- the library's argument checks (no GPU) ----------------------------------------------------------------------------------
+def _struct(**kw):
+    from bayesml_amd import _mtree
+    base = dict(n_trees=1, n_nodes=3, n_thr=3, max_tree_nodes=3, max_children=2, max_depth=1, dim_cont=1, dim_cat=0,
+                tree_off_dev=64, feat_dev=64, child0_dev=64, nchild_dev=64, thr_off_dev=64, depth_dev=64, thr_dev=64)
+    base.update(kw)
+    return _mtree.ForestStruct(**base)
+
+
+def test_header_and_ctypes_table_agree():
+    import re
+    from bayesml_amd import _mtree
+    from conftest import ROOT
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mtree.h")).read(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(mtree_[a-z0-9_]+)\s*\(", text))) == sorted(_mtree.SYMBOLS)
+    for name, value in (("MTREE_MAX_TREES", _mtree.MAX_TREES), ("MTREE_MAX_NODES", _mtree.MAX_NODES),
+                        ("MTREE_MAX_CHILDREN", _mtree.MAX_CHILDREN), ("MTREE_MAX_DEGREE", _mtree.MAX_DEGREE),
+                        ("MTREE_MAX_DEPTH", _mtree.MAX_DEPTH), ("MTREE_MAX_SLABS", _mtree.MAX_SLABS),
+                        ("MTREE_LDS_SLOTS", _mtree.LDS_SLOTS)):
+        assert re.search(rf"#define {name} {value}\b", text), name
+
+
+def test_mtree_argument_checks_without_gpu():
+    from bayesml_amd import _mtree
+    lib = _mtree.load_library()
+    assert lib.mtree_abi_version() == 1
+    ni, nr, npost = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    for fam in range(5):
+        assert lib.mtree_stat_cols(fam, 3, ni, nr, npost) == 0
+        assert (ni.value, nr.value, npost.value) == _mtree.stat_cols(fam, 3)
+    assert lib.mtree_stat_cols(7, 0, ni, nr, npost) == 1 and lib.mtree_stat_cols(_mtree.CATEGORICAL, 17, ni, nr, npost) == 2
+    assert lib.mtree_work_len(10, _mtree.NORMAL, 0, 4) == 10 * (1 + 4 * 2) and lib.mtree_work_len(10, 0, 0, 65) == -1
+    ok = _struct()
+    route = lambda f, n=8, stop=64, bad=64, xc=64, dt=_mtree.F64: lib.mtree_route(      # noqa: E731
+        ctypes.byref(f), dt, xc, _mtree.U8, None, None, n, stop, None, bad, None)
+    # (every call below is refused before anything touches the device: the pointers are made-up addresses)
+    assert route(ok, n=0) == 1 and b"n must be >= 1" in lib.mtree_last_error()
+    assert route(ok, stop=None) == 1 and route(ok, xc=None) == 1 and route(ok, dt=_mtree.U8) == 1
+    assert route(ok, xc=68) == 1 and b"aligned" in lib.mtree_last_error()
+    assert route(_struct(n_trees=0)) == 1 and route(_struct(feat_dev=None)) == 1 and route(_struct(thr_dev=68)) == 1
+    for over in (dict(n_trees=1025, n_nodes=2000), dict(max_tree_nodes=4097, n_nodes=5000), dict(max_children=17),
+                 dict(max_depth=25)):
+        assert route(_struct(**over)) == 2 and b"not supported" in lib.mtree_last_error()
+    assert lib.mtree_reduce(ctypes.byref(ok), 0, 0, 64, 64, None, 8, 0, 64, 64, 64, None) == 1
+    assert lib.mtree_reduce(ctypes.byref(ok), 0, 0, 64, None, None, 8, 1, 64, 64, 64, None) == 1
+    assert lib.mtree_reduce(ctypes.byref(ok), 1, 17, 64, 64, None, 8, 1, 64, 64, 64, None) == 2
+    assert lib.mtree_sweep(ctypes.byref(ok), 0, 0, 64, 64, None, None, 64, 64, 64, 64, 64, 64, None) == 1
+    assert lib.mtree_predict(ctypes.byref(ok), _mtree.BERNOULLI, 0, _mtree.PRED_MEAN, _mtree.F64, 64, 0, None, 8, 64, 64, 64,
+                             64, 64, None) == 1 and b"no such read-out" in lib.mtree_last_error()
+    assert lib.mtree_predict(ctypes.byref(ok), _mtree.POISSON, 0, _mtree.PRED_VAR, _mtree.F64, 64, 0, None, 8, 64, 64, 64, 64,
+                             64, None) == 1
+    assert lib.mtree_predict(ctypes.byref(ok), _mtree.NORMAL, 0, 9, _mtree.F64, 64, 0, None, 8, 64, 64, 64, 64, 64, None) == 1
+
+
+def test_limits_raise_engine_limit_error():
+    from bayesml_amd import _mtree
+    from bayesml_amd._engine import EngineLimitError
+    _mtree.check_limits(1024, 2047, 2, 10)           # binary trees of depth 10 and 1024 trees fit
+    for args in ((1025, 10, 2, 3), (1, 4097, 2, 3), (1, 10, 17, 3), (1, 10, 2, 25), (1, 10, 2, 3, 17)):
+        with pytest.raises(EngineLimitError, match="bayesml itself has no such limit"):
+            _mtree.check_limits(*args)
+    assert _mtree.slabs_for(1, 100, 2) == 1 and _mtree.slabs_for(1025, 100, 2) == 2 and _mtree.slabs_for(10 ** 7, 100, 2) == 64
+    assert _mtree.slabs_for(10 ** 7, 1024 * 2047, 3) == 10
+
+
+def test_there_is_no_cpu_fallback():
+    from bayesml_amd import metatree
+    from bayesml_amd._engine import EngineUnavailableError
+    assert metatree.LearnModel._mtree_pass_factory is None
+    flat, g = orc._hand_forest()
+    sub = _subs()["bernoulli"]
+    m = metatree.LearnModel(SubModel=sub, device="cpu", **orc._HAND)          # (refused with or without a GPU in the box)
+    m.set_hn_params(hn_metatree_list=orc.nodes_from_flat(metatree, flat, g, sub.LearnModel))      # host only
+    inp = orc.case_inputs(CASE["threeway"])
+    with pytest.raises(EngineUnavailableError):
+        m.update_posterior(inp["xc1"], inp["xk1"], inp["y1"], alg_type="given_MT")
