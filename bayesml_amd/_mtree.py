@@ -73,7 +73,7 @@ def load_library() -> ctypes.CDLL:
 def stat_cols(family: int, degree: int = 0):
     """(int64 columns, float64 columns, length of the posterior vector) of a family: include/mtree.h, mtree_stat_cols."""
     return {BERNOULLI: (2, 0, 2), CATEGORICAL: (1 + degree, 0, degree), POISSON: (2, 1, 3), EXPONENTIAL: (1, 1, 2),
-            NORMAL: (1, 2, 5)}[family]
+            NORMAL: (1, 3, 5)}[family]
 
 
 @dataclass
@@ -124,6 +124,7 @@ def check_limits(n_trees: int, max_tree_nodes: int, max_children: int, max_depth
 
 def slabs_for(n: int, n_nodes: int, cols: int) -> int:
     """Row slabs of one reduction: one per MIN_SPAN rows, at most MAX_SLABS, and scratch below WORK_SLOTS."""
+    assert n >= 1 and n_nodes >= 1 and cols >= 1
     return int(max(1, min(MAX_SLABS, -(-n // MIN_SPAN), WORK_SLOTS // max(1, n_nodes * cols))))
 
 
@@ -217,22 +218,21 @@ class MtreePass:
             self._work = torch.empty(need, dtype=torch.int64, device=self.device)
         return self._work
 
-    def reduce(self, stop, y, pivot=None):
+    def reduce(self, stop, y):
         n = int(stop.shape[1])
         S = slabs_for(n, self.flat.n_nodes, self.ni + min(self.nr, 1))
         work = self._scratch(S)
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_reduce(ctypes.byref(self.struct), self.family, self.degree, stop.data_ptr(), y.data_ptr(),
-                                       _ptr(pivot), n, S, self.stat_int.data_ptr(), self.stat_real.data_ptr(), work.data_ptr(),
-                                       self._stream())
+                                       None, n, S, self.stat_int.data_ptr(), self.stat_real.data_ptr(), work.data_ptr(), self._stream())
         _check(self.lib, rc, "mtree_reduce")
 
-    def sweep(self, pivot=None):
+    def sweep(self):
         work = self._scratch(1)
         lnp = torch.log(self.prob)
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_sweep(ctypes.byref(self.struct), self.family, self.degree, self.stat_int.data_ptr(),
-                                      self.stat_real.data_ptr(), _ptr(pivot), self.h0.data_ptr(), self.post.data_ptr(),
+                                      self.stat_real.data_ptr(), None, self.h0.data_ptr(), self.post.data_ptr(),
                                       self.g.data_ptr(), self.lml.data_ptr(), self.lcm.data_ptr(), lnp.data_ptr(), work.data_ptr(),
                                       self._stream())
         _check(self.lib, rc, "mtree_sweep")
@@ -244,9 +244,8 @@ class MtreePass:
         stop, _, bad = self.route(xc, xk)
         n, bad = int(stop.shape[1]), int(bad.cpu()[0])
         if bad == 0:
-            pivot = y[:1].clone() if self.family == NORMAL else None
-            self.reduce(stop, y, pivot)
-            self.sweep(pivot)
+            self.reduce(stop, y)
+            self.sweep()
             self.launch_info = "mtree_route + mtree_reduce + mtree_sweep"
         return n, bad
 
@@ -280,7 +279,7 @@ class MtreePass:
             getattr(self, name).copy_(torch.from_numpy(np.ascontiguousarray(s[name], dtype=np.float64)))
 
     def last_stats(self):
-        """The statistics tables after the last update (subtree totals), for tests."""
+        """The statistics tables after the last update (subtree totals; normal: mu, c, SS of include/mtree.h), for tests."""
         return self.stat_int.cpu().numpy(), self.stat_real.cpu().numpy()[:, :self.nr]
 
     def close(self):

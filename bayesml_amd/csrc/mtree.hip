@@ -35,7 +35,7 @@ static int cols_of(int family, int degree, Cols* c) {
         case MTREE_CATEGORICAL: *c = {1 + degree, 0, degree}; break;
         case MTREE_POISSON: *c = {2, 1, 3}; break;
         case MTREE_EXPONENTIAL: *c = {1, 1, 2}; break;
-        default: *c = {1, 2, 5}; break;
+        default: *c = {1, 3, 5}; break;
     }
     return MTREE_OK;
 }
@@ -141,7 +141,7 @@ int mtree_stat_cols(int family, int degree, int* n_int, int* n_real, int* n_post
 int64_t mtree_work_len(int32_t n_nodes, int family, int degree, int n_slabs) {
     Cols c;
     if (cols_of(family, degree, &c) != MTREE_OK || n_nodes < 1 || n_slabs < 1 || n_slabs > MTREE_MAX_SLABS) return -1;
-    // [ L of the sweep | integer slabs | real slabs (one column at a time for normal's two passes) ]
+    // [ L of the sweep | integer slabs | real slabs ]; normal's second pass (two real columns) takes the place of both
     return (int64_t)n_nodes * (1 + (int64_t)n_slabs * (c.ni + (c.nr > 1 ? 1 : c.nr)));
 }
 
@@ -187,12 +187,12 @@ int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* s
     const bool lds1 = lds_path(f, c.ni + nr1);
     if (lds1) {
         hipLaunchKernelGGL((reduce_kernel<true>), grid, dim3(kWave), sizeof(double) * (size_t)f->max_tree_nodes * (c.ni + nr1), st,
-                           F, family, degree, c.ni, nr1, stop_dev, y_dev, pivot_dev, n, S, wi, wr);
+                           F, family, degree, c.ni, nr1, stop_dev, y_dev, (const double*)nullptr, n, S, wi, wr);
     } else {
         const hipError_t e = hipMemsetAsync(wi, 0, sizeof(double) * (size_t)S * F.n_nodes * (c.ni + nr1), st);
         if (e != hipSuccess) return fail(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
         hipLaunchKernelGGL((reduce_kernel<false>), grid, dim3(kWave), 0, st, F, family, degree, c.ni, nr1, stop_dev, y_dev,
-                           pivot_dev, n, S, wi, wr);
+                           (const double*)nullptr, n, S, wi, wr);
     }
     if (int rc = launched("reduce_kernel launch")) return rc;
     hipLaunchKernelGGL((combine_kernel<int64_t>), dim3(grid_of((int64_t)F.n_nodes * c.ni)), dim3(kThreads), 0, st,
@@ -204,12 +204,22 @@ int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* s
         if (int rc = launched("combine_kernel launch")) return rc;
     }
     if (family != MTREE_NORMAL) return MTREE_OK;
-    // (one column per node: every tree within MTREE_MAX_NODES fits the LDS table, mtree_kernels.h)
-    hipLaunchKernelGGL(reduce_ss_kernel, grid, dim3(kWave), sizeof(double) * (size_t)MTREE_MAX_NODES, st, F, stop_dev,
-                       (const double*)y_dev, pivot_dev, n, S, (const int64_t*)stat_int_dev, (const double*)stat_real_dev, wr);
-    if (int rc = launched("reduce_ss_kernel launch")) return rc;
-    hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of(F.n_nodes)), dim3(kThreads), 0, st, (const double*)wr, S,
-                       (int64_t)F.n_nodes, 1, c.nr, 1, stat_real_dev);
+    // The second pass: two columns per node, in the scratch of the first pass (ni + 1 = 2 columns, combined already).
+    static_assert(sizeof(unsigned long long) == sizeof(double), "the two passes share the slabs");
+    double* w2 = (double*)wi;
+    if (lds_path(f, 2)) {
+        hipLaunchKernelGGL((reduce_centred_kernel<true>), grid, dim3(kWave), sizeof(double) * (size_t)f->max_tree_nodes * 2, st, F,
+                           stop_dev, (const double*)y_dev, n, S, (const int64_t*)stat_int_dev, (const double*)stat_real_dev, c.nr,
+                           w2);
+    } else {
+        const hipError_t e = hipMemsetAsync(w2, 0, sizeof(double) * (size_t)S * F.n_nodes * 2, st);
+        if (e != hipSuccess) return fail(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
+        hipLaunchKernelGGL((reduce_centred_kernel<false>), grid, dim3(kWave), 0, st, F, stop_dev, (const double*)y_dev, n, S,
+                           (const int64_t*)stat_int_dev, (const double*)stat_real_dev, c.nr, w2);
+    }
+    if (int rc = launched("reduce_centred_kernel launch")) return rc;
+    hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of((int64_t)F.n_nodes * 2)), dim3(kThreads), 0, st, (const double*)w2,
+                       S, (int64_t)F.n_nodes, 2, c.nr, 1, stat_real_dev);
     return launched("combine_kernel launch");
 }
 
@@ -227,7 +237,7 @@ int mtree_sweep(const mtree_forest* f, int family, int degree, int64_t* stat_int
         (uintptr_t)work_dev % 8)
         return fail(MTREE_EINVAL, "mtree_sweep: misaligned pointer");
     hipLaunchKernelGGL(sweep_kernel, dim3((unsigned)F.n_trees), dim3(kThreads), 0, (hipStream_t)stream, F, family, degree, c.ni,
-                       c.nr, c.np, stat_int_dev, stat_real_dev, pivot_dev, h0_dev, post_dev, g_dev, lml_dev, lcm_dev, lnp_dev,
+                       c.nr, c.np, stat_int_dev, stat_real_dev, h0_dev, post_dev, g_dev, lml_dev, lcm_dev, lnp_dev,
                        (double*)work_dev);
     return launched("sweep_kernel launch");
 }

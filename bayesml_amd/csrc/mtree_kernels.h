@@ -3,7 +3,7 @@
 //
 // (a) route_kernel<TC, TK>: one thread per (row, tree); blockIdx.y is the tree, so a wave walks one tree and its node reads
 //     stay in a few cache lines near the root.  The rows' features are read where they lie; adjacent lanes read adjacent rows.
-// (b) reduce_kernel<LDSH> / reduce_ss_kernel: a workgroup is ONE wave and owns a contiguous slab of rows of one tree
+// (b) reduce_kernel<LDSH> / reduce_centred_kernel<LDSH>: a workgroup is ONE wave and owns a contiguous slab of rows of one tree
 //     and a table only it writes (LDS when the tree's table fits MTREE_LDS_SLOTS, else its slab of global scratch, zeroed
 //     by the caller).  Integer columns are integer atomics.  For a real column the wave takes 64 rows at a time; while lanes
 //     remain, the first remaining lane's node id is broadcast, the lanes that share it are balloted, their addends (0.0 in
@@ -117,6 +117,31 @@ __device__ inline void wave_group_add(double* table, int stride, int key, bool a
     }
 }
 
+// The same rounds for two columns of one entry (table[key * stride] += a, table[key * stride + 1] += b).
+__device__ inline void wave_group_add2(double* table, int stride, int key, bool active, double a, double b) {
+    unsigned long long rest = __ballot(active);
+    const int lane = threadIdx.x & 63;
+    while (rest) {
+        const int lead = __ffsll((long long)rest) - 1;
+        const int k0 = __shfl(key, lead);
+        const bool in = active && key == k0;
+        const unsigned long long same = __ballot(in);
+        double s = in ? a : 0.0, q = in ? b : 0.0;
+        if (__popcll(same) > 1) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                s += __shfl_xor(s, off);
+                q += __shfl_xor(q, off);
+            }
+        }
+        if (lane == lead) {
+            table[(int64_t)k0 * stride] += s;
+            table[(int64_t)k0 * stride + 1] += q;
+        }
+        rest &= ~same;
+    }
+}
+
 struct Slab {
     int64_t lo, hi;
 };
@@ -150,6 +175,7 @@ __global__ __launch_bounds__(kWave) void reduce_kernel(Forest f, int family, int
         __syncthreads();
     }
     const Slab sl = slab_of(n, S, s);
+    // (pivot: a value taken off every y of normal before it is summed; mtree_reduce passes none)
     const double pv = (family == MTREE_NORMAL && pivot) ? pivot[0] : 0.0;
     const bool discrete = family <= MTREE_POISSON;
     for (int64_t base = sl.lo; base < sl.hi; base += kWave) {
@@ -183,40 +209,43 @@ __global__ __launch_bounds__(kWave) void reduce_kernel(Forest f, int family, int
     }
 }
 
-// The second pass of normal: sum of (y - pivot - mean of the stop node)^2, mean = stat_real[node][0] / stat_int[node][0] of
-// the combined first pass.  work_real: [S][n_nodes][1].  One column: the table of any tree within MTREE_MAX_NODES fits LDS.
-static_assert(MTREE_MAX_NODES <= MTREE_LDS_SLOTS, "reduce_ss_kernel keeps a tree's one-column table in LDS");
-__global__ __launch_bounds__(kWave) void reduce_ss_kernel(Forest f, const int32_t* __restrict__ stop,
-                                                          const double* __restrict__ y, const double* __restrict__ pivot,
-                                                          int64_t n, int S, const int64_t* __restrict__ stat_int,
-                                                          const double* __restrict__ stat_real,
-                                                          double* __restrict__ work_real) {
+// The second pass of normal.  mu = stat_real[node][0] / stat_int[node][0] of the combined first pass is the stop node's own
+// expansion point: the pass sums r = y - mu and r^2 (work_real: [S][n_nodes][2]).  The node's mean is mu + (sum r) / n, so
+// what the plain sum of the first pass lost comes back in sum r, and no row is ever measured from another node's level.
+template <bool LDSH>
+__global__ __launch_bounds__(kWave) void reduce_centred_kernel(Forest f, const int32_t* __restrict__ stop,
+                                                               const double* __restrict__ y, int64_t n, int S,
+                                                               const int64_t* __restrict__ stat_int,
+                                                               const double* __restrict__ stat_real, int nr,
+                                                               double* __restrict__ work_real) {
     extern __shared__ __align__(16) unsigned char lds[];
     const int b = blockIdx.y, s = blockIdx.x, lane = threadIdx.x;
     const int t0 = f.tree_off[b], nn = f.tree_off[b + 1] - t0;
     if (t0 < 0 || nn < 1 || nn > MTREE_MAX_NODES || t0 + nn > f.n_nodes) return;
-    double* gr = work_real + ((int64_t)s * f.n_nodes + t0);
-    double* tr = (double*)lds;
-    for (int j = lane; j < nn; j += kWave) tr[j] = 0.0;
-    __syncthreads();
+    double* gr = work_real + ((int64_t)s * f.n_nodes + t0) * 2;
+    double* tr = LDSH ? (double*)lds : gr;
+    if (LDSH) {
+        for (int j = lane; j < nn * 2; j += kWave) tr[j] = 0.0;
+        __syncthreads();
+    }
     const Slab sl = slab_of(n, S, s);
-    const double pv = pivot ? pivot[0] : 0.0;
     for (int64_t base = sl.lo; base < sl.hi; base += kWave) {
         const int64_t i = base + lane;
         bool active = i < sl.hi;
         int key = active ? stop[(int64_t)b * n + i] - t0 : -1;
         active = active && key >= 0 && key < nn;
-        double rv = 0.0;
+        double r = 0.0;
         if (active) {
             const int64_t cnt = stat_int[t0 + key];
-            const double mean = cnt > 0 ? stat_real[(int64_t)(t0 + key) * 2] / (double)cnt : 0.0;
-            const double d = (y[i] - pv) - mean;
-            rv = d * d;
+            const double mu = cnt > 0 ? stat_real[(int64_t)(t0 + key) * nr] / (double)cnt : 0.0;
+            r = y[i] - mu;
         }
-        wave_group_add(tr, 1, key, active, rv);
+        wave_group_add2(tr, 2, key, active, r, r * r);
     }
-    __syncthreads();
-    for (int j = lane; j < nn; j += kWave) gr[j] = tr[j];
+    if (LDSH) {
+        __syncthreads();
+        for (int j = lane; j < nn * 2; j += kWave) gr[j] = tr[j];
+    }
 }
 
 // out[node * out_stride + out_col + c] = sum over slabs, in slab order, of work[(s * n_nodes + node) * cols + c].
@@ -235,50 +264,77 @@ __global__ __launch_bounds__(kThreads) void combine_kernel(const T* __restrict__
 // ---- (c) ------------------------------------------------------------------------------------------------------------------
 // Children's totals into node v's (in place), then the fold and lml.  Returns false (nothing written) when n = 0.
 __device__ inline bool fold_node(const Forest& f, int family, int degree, int ni, int nr, int np, int v, int lo, int hi,
-                                 int64_t* __restrict__ si, double* __restrict__ sr, double pv, const double* __restrict__ h0,
+                                 int64_t* __restrict__ si, double* __restrict__ sr, const double* __restrict__ h0,
                                  double* __restrict__ post, double* lml_out) {
     int64_t* ci = si + (int64_t)v * ni;
     double* cr = sr + (int64_t)v * nr;
     const int nc = f.feat[v] >= 0 ? f.nchild[v] : 0;
     const int c0 = f.child0[v];
     const bool kids = nc > 0 && nc <= MTREE_MAX_CHILDREN && c0 > v && c0 >= lo && c0 + nc <= hi;
-    if (kids) {
+    if (family == MTREE_NORMAL) {
+        // A node's three columns are (mu, c, SS): its mean is mu + c / n and SS is about that mean.  The reduction left
+        // (sum y, sum r, sum r^2) of the node's own rows, r = y - mu with mu = (sum y) / n: sum (r - c/n)^2 = sum r^2 - c^2/n.
         const int64_t n_own = ci[0];
+        double mu = 0.0, c = 0.0, ss = 0.0;
+        if (n_own > 0) {
+            mu = cr[0] / (double)n_own;
+            c = cr[1];
+            ss = fmax(cr[2] - c * c / (double)n_own, 0.0);
+        }
         int64_t n_tot = n_own;
-        for (int c = 0; c < nc; ++c) n_tot += si[(int64_t)(c0 + c) * ni];
-        if (family == MTREE_NORMAL) {
-            double sum = cr[0];
-            for (int c = 0; c < nc; ++c) sum += sr[(int64_t)(c0 + c) * nr];
-            if (n_tot > 0) {
-                const double mean = sum / (double)n_tot;
-                double ss = 0.0;
-                if (n_own > 0) {
-                    const double dm = cr[0] / (double)n_own - mean;
-                    ss += cr[1] + (double)n_own * dm * dm;
+        if (kids)
+            for (int k = 0; k < nc; ++k) n_tot += si[(int64_t)(c0 + k) * ni];
+        if (n_tot > n_own) {
+            // The parts (own rows, children) merge about muP, the rounded mean of them all, so that every n (mu - muP) is
+            // known to an ulp of sum |y|; cP takes what is left.  All dm use the same cP / n, whose error therefore enters
+            // SS only squared.
+            double w = n_own > 0 ? (double)n_own * (mu + c / (double)n_own) : 0.0;
+            for (int k = 0; k < nc; ++k) {
+                const int64_t n_c = si[(int64_t)(c0 + k) * ni];
+                const double* kr = sr + (int64_t)(c0 + k) * nr;
+                if (n_c > 0) w += (double)n_c * (kr[0] + kr[1] / (double)n_c);
+            }
+            const double muP = w / (double)n_tot;
+            double cP = n_own > 0 ? c + (double)n_own * (mu - muP) : 0.0;
+            for (int k = 0; k < nc; ++k) {
+                const int64_t n_c = si[(int64_t)(c0 + k) * ni];
+                const double* kr = sr + (int64_t)(c0 + k) * nr;
+                if (n_c > 0) cP += kr[1] + (double)n_c * (kr[0] - muP);
+            }
+            const double off = cP / (double)n_tot;
+            double ssP = 0.0;
+            if (n_own > 0) {
+                const double dm = (mu - muP) + (c / (double)n_own - off);
+                ssP += ss + (double)n_own * dm * dm;
+            }
+            for (int k = 0; k < nc; ++k) {
+                const int64_t n_c = si[(int64_t)(c0 + k) * ni];
+                const double* kr = sr + (int64_t)(c0 + k) * nr;
+                if (n_c > 0) {
+                    const double dm = (kr[0] - muP) + (kr[1] / (double)n_c - off);
+                    ssP += kr[2] + (double)n_c * dm * dm;
                 }
-                for (int c = 0; c < nc; ++c) {
-                    const int64_t n_c = si[(int64_t)(c0 + c) * ni];
-                    if (n_c > 0) {
-                        const double* kr = sr + (int64_t)(c0 + c) * nr;
-                        const double dm = kr[0] / (double)n_c - mean;
-                        ss += kr[1] + (double)n_c * dm * dm;
-                    }
-                }
-                cr[1] = ss;
             }
-            cr[0] = sum;
-            ci[0] = n_tot;
-        } else {
-            for (int j = 0; j < ni; ++j) {
-                int64_t t = ci[j];
-                for (int c = 0; c < nc; ++c) t += si[(int64_t)(c0 + c) * ni + j];
-                ci[j] = t;
-            }
-            for (int j = 0; j < nr; ++j) {
-                double t = cr[j];
-                for (int c = 0; c < nc; ++c) t += sr[(int64_t)(c0 + c) * nr + j];
-                cr[j] = t;
-            }
+            mu = muP;
+            c = cP;
+            ss = ssP;
+        }
+        if (n_tot > 0) {
+            cr[0] = mu;
+            cr[1] = c;
+            cr[2] = ss;
+        }
+        ci[0] = n_tot;
+    } else if (kids) {
+        for (int j = 0; j < ni; ++j) {
+            int64_t t = ci[j];
+            for (int c = 0; c < nc; ++c) t += si[(int64_t)(c0 + c) * ni + j];
+            ci[j] = t;
+        }
+        for (int j = 0; j < nr; ++j) {
+            double t = cr[j];
+            for (int c = 0; c < nc; ++c) t += sr[(int64_t)(c0 + c) * nr + j];
+            cr[j] = t;
         }
     }
     const int64_t n = ci[0];
@@ -310,8 +366,9 @@ __device__ inline bool fold_node(const Forest& f, int family, int degree, int ni
         p[1] += cr[0];
         lml = h0[0] * log(h0[1]) - lgamma_call(h0[0]) - p[0] * log(p[1]) + lgamma_call(p[0]);
     } else {
-        const double dn = (double)n, x_bar = pv + cr[0] / dn, dm = x_bar - p[0];
-        p[3] += (cr[1] + dn * p[1] / (p[1] + dn) * (dm * dm)) / 2.0;
+        // (the difference to the prior mean from mu, not from the rounded x_bar: m and mu may be close)
+        const double dn = (double)n, off = cr[1] / dn, x_bar = cr[0] + off, dm = (cr[0] - p[0]) + off;
+        p[3] += (cr[2] + dn * p[1] / (p[1] + dn) * (dm * dm)) / 2.0;
         p[0] = (p[1] * p[0] + dn * x_bar) / (p[1] + dn);
         p[1] += dn;
         p[2] += dn * 0.5;
@@ -326,19 +383,17 @@ __device__ inline bool fold_node(const Forest& f, int family, int degree, int ni
 // grid n_trees, kThreads threads.  L: [n_nodes] scratch.
 __global__ __launch_bounds__(kThreads) void sweep_kernel(Forest f, int family, int degree, int ni, int nr, int np,
                                                          int64_t* __restrict__ si, double* __restrict__ sr,
-                                                         const double* __restrict__ pivot, const double* __restrict__ h0,
-                                                         double* __restrict__ post, double* __restrict__ g,
+                                                         const double* __restrict__ h0, double* __restrict__ post, double* __restrict__ g,
                                                          double* __restrict__ lml, double* __restrict__ lcm,
                                                          double* __restrict__ lnp, double* __restrict__ L) {
     const int b = blockIdx.x;
     const int lo = f.tree_off[b], hi = f.tree_off[b + 1];
     if (lo < 0 || hi > f.n_nodes || lo >= hi) return;       // (uniform over the workgroup)
-    const double pv = (family == MTREE_NORMAL && pivot) ? pivot[0] : 0.0;
     for (int d = f.max_depth; d >= 0; --d) {
         for (int v = lo + threadIdx.x; v < hi; v += kThreads) {
             if (f.depth[v] != d) continue;
             double own = 0.0;
-            if (!fold_node(f, family, degree, ni, nr, np, v, lo, hi, si, sr, pv, h0, post, &own)) {
+            if (!fold_node(f, family, degree, ni, nr, np, v, lo, hi, si, sr, h0, post, &own)) {
                 L[v] = 0.0;
                 continue;
             }

@@ -80,7 +80,7 @@ const char* mtree_last_error(void);
  *   categorical  int [n, c_0..c_{deg-1}]   real -                         post [alpha_0..alpha_{deg-1}]
  *   poisson      int [n, sum y]            real [sum ln y!]               post [alpha, beta, sum ln y!]
  *   exponential  int [n]                   real [sum y]                   post [alpha, beta]
- *   normal       int [n]                   real [sum (y - pivot), SS]     post [m, kappa, alpha, beta, n]
+ *   normal       int [n]                   real [mu, c, SS]               post [m, kappa, alpha, beta, n]
  * Returns 0, or MTREE_EINVAL / MTREE_EUNSUPPORTED for an unknown family or a degree outside 1..MTREE_MAX_DEGREE. */
 int mtree_stat_cols(int family, int degree, int* n_int, int* n_real, int* n_post);
 /* 8-byte slots of scratch for mtree_reduce and mtree_sweep with n_slabs slabs (one buffer serves both); -1 on bad arguments. */
@@ -96,22 +96,26 @@ int mtree_route(const mtree_forest* f, int xc_dtype, const void* xc_dev, int xk_
 
 /* Per (tree, stop node), the statistics of the y of the rows that stop there, into stat_int_dev[n_nodes][n_int] and
  * stat_real_dev[n_nodes][n_real] (overwritten).  y_dev: n values, int64 for bernoulli / categorical / poisson, binary64 for
- * exponential / normal; a value outside the family's support is left out of every column but n.  pivot_dev: NULL or one
- * binary64 that is subtracted from every y of the normal family before it is summed.  Integer columns are integer atomics
- * (exact, order-free).  Real columns use no floating-point atomics and are bit-reproducible: a wave owns a contiguous slab
- * of rows of one tree and a table only it writes, adds the lanes that share a node in fixed lane order, and the slabs are
- * added in slab order.  For normal a second pass sums (y - mean of the stop node)^2. */
+ * exponential / normal; a value outside the family's support is left out of every column but n.  Integer columns are
+ * integer atomics (exact, order-free).  Real columns use no floating-point atomics and are bit-reproducible: a wave owns a
+ * contiguous slab of rows of one tree and a table only it writes, adds the lanes that share a node in fixed lane order, and
+ * the slabs are added in slab order.  Normal takes two passes and no pivot that nodes would share: the first sums y per stop
+ * node, the second sums r = y - mu and r^2 about the node's own mu = (sum y) / n, and leaves [sum y, sum r, sum r^2].
+ * pivot_dev: NULL or an 8-byte aligned pointer; it is not read (the place of the batch-wide pivot the signature once took). */
 int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev,
                  const double* pivot_dev, int64_t n, int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev,
                  void* stream);
 
 /* One launch, a workgroup per tree, depth by depth from the deepest to the root.  In place: the statistics become subtree
- * totals (children added in child order; normal merges SS = sum_c [SS_c + n_c (mean_c - mean)^2]); a node with n = 0 is left
+ * totals (children added in child order).  A normal node carries [mu, c, SS]: its mean is mu + c / n, formed once, at the
+ * fold, and SS is about that mean; the parts of a node (its own rows, its children) merge about mu_P = their rounded common
+ * mean, c_P = sum [c_i + n_i (mu_i - mu_P)], SS_P = sum [SS_i + n_i dm_i^2], dm_i = (mu_i - mu_P) + (c_i / n_i - c_P / n_P).
+ * A node with n = 0 is left
  * bit-identical and its parent takes 0.0 for it; every other node gets its posterior folded (post_dev[n_nodes][n_post]),
  * lml_dev[node] = the family's log marginal likelihood of the folded posterior against h0_dev[n_post], and an inner node
  * g <- exp(t1 - L), t1 = ln g + sum of the children's L, L = logaddexp(ln(1 - g) + lml, t1); g = 0 and g = 1 are fixed
  * points.  lcm_dev[c] = the L (0.0 for an empty child) that the visited parent of node c took for it, the reference's
- * log_children_marginal_likelihood.  lnp_dev[b] += L of the root. */
+ * log_children_marginal_likelihood.  lnp_dev[b] += L of the root.  pivot_dev: as in mtree_reduce, not read. */
 int mtree_sweep(const mtree_forest* f, int family, int degree, int64_t* stat_int_dev, double* stat_real_dev,
                 const double* pivot_dev, const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev,
                 double* lcm_dev, double* lnp_dev, void* work_dev, void* stream);

@@ -172,6 +172,213 @@ def batch_update(flat, state, fam, degree, h0, dim_cont, xc, xk, y):
     return st, counts
 
 
+# ---- the reference's own per-node float64 form, and deviations per node and column ------------------------------------------
+def node_rows(flat, dim_cont, xc, xk):
+    """rows[v]: the boolean mask of the batch rows whose walk passes node v (None where no row does)."""
+    paths = route(flat, dim_cont, xc, xk)
+    rows = [None] * len(flat["feat"])
+    for b in range(paths.shape[0]):
+        for d in range(paths.shape[2]):
+            col = paths[b, :, d]
+            for v in np.unique(col[col >= 0]):
+                rows[int(v)] = col == v
+    return rows
+
+
+def _plain_lml(fam, h0, p, extra):
+    """calc_log_marginal_likelihood of the scalar learners as they write it, in float64."""
+    from scipy.special import gammaln
+    if fam == BERNOULLI:
+        return gammaln(h0[0] + h0[1]) - gammaln(h0[0]) - gammaln(h0[1]) - gammaln(p[0] + p[1]) + gammaln(p[0]) + gammaln(p[1])
+    if fam == CATEGORICAL:
+        return gammaln(h0.sum()) - gammaln(h0).sum() - gammaln(p.sum()) + gammaln(p).sum()
+    if fam == POISSON:
+        return h0[0] * np.log(h0[1]) - gammaln(h0[0]) - p[0] * np.log(p[1]) + gammaln(p[0]) - extra
+    if fam == EXPONENTIAL:
+        return h0[0] * np.log(h0[1]) - gammaln(h0[0]) - p[0] * np.log(p[1]) + gammaln(p[0])
+    return (h0[2] * np.log(h0[3]) - p[2] * np.log(p[3]) + gammaln(p[2]) - gammaln(h0[2])
+            + 0.5 * (np.log(h0[1]) - np.log(p[1]) - extra * np.log(2 * np.pi)))
+
+
+def _plain_fold(fam, degree, p, ys):
+    """_update_posterior of the scalar learners on the post vector p (float64), from the node's rows alone."""
+    from scipy.special import gammaln
+    n = ys.size
+    p = p.copy()
+    if fam == BERNOULLI:
+        ones = np.count_nonzero(ys == 1)
+        p[0] += ones
+        p[1] += n - ones
+    elif fam == CATEGORICAL:
+        for a in range(degree):
+            p[a] += np.count_nonzero(ys == a)
+    elif fam == POISSON:
+        p[0] += ys.sum()
+        p[1] += n
+        p[2] += gammaln(ys + 1).sum()
+    elif fam == EXPONENTIAL:
+        p[0] += n
+        p[1] += ys.sum()
+    else:
+        x_bar = ys.sum() / n
+        p[3] += (((ys - x_bar) ** 2).sum() + n * p[1] / (p[1] + n) * (x_bar - p[0]) ** 2) / 2.0
+        p[0] = (p[1] * p[0] + n * x_bar) / (p[1] + n)
+        p[1] += n
+        p[2] += n * 0.5
+        p[4] += n
+    return p
+
+
+def plain_update(flat, state, fam, degree, h0, dim_cont, xc, xk, y):
+    """``batch_update`` as the reference computes it: per node from that node's rows, every formula in float64 numpy
+    (x_bar = y.sum() / n, ((y - x_bar) ** 2).sum(), scipy's gammaln, np.logaddexp).  Its deviation from the exact state is
+    what plain float64 costs on a case: the yardstick ``e_plain`` of the GPU tests."""
+    st = {k: np.array(v, dtype=np.float64) for k, v in state.items()}
+    rows = node_rows(flat, dim_cont, xc, xk)
+    y, h0 = np.asarray(y), np.asarray(h0, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        lnp = np.log(st["prob"])
+    for b in range(len(flat["tree_off"]) - 1):
+        lo, hi = int(flat["tree_off"][b]), int(flat["tree_off"][b + 1])
+        L = {}
+        for v in range(hi - 1, lo - 1, -1):
+            if rows[v] is None:
+                continue
+            p = _plain_fold(fam, degree, st["post"][v], y[rows[v]])
+            lml = _plain_lml(fam, h0, p, p[4] if fam == NORMAL else p[2] if fam == POISSON else 0.0)
+            st["post"][v], st["lml"][v] = p, lml
+            if flat["feat"][v] < 0:
+                L[v] = lml
+                continue
+            kids = range(int(flat["child0"][v]), int(flat["child0"][v]) + int(flat["nchild"][v]))
+            lc = np.array([L.get(c, 0.0) for c in kids])
+            st["lcm"][kids.start:kids.stop] = lc
+            with np.errstate(divide="ignore"):
+                t1 = np.log(st["g"][v]) + lc.sum()
+                L[v] = np.logaddexp(np.log(1 - st["g"][v]) + lml, t1)
+            st["g"][v] = np.exp(t1 - L[v])
+        lnp[b] += L[lo]
+    w = np.exp(lnp - lnp.max())
+    st["prob"] = w / w.sum()
+    return st
+
+
+def m_scales(flat, state, dim_cont, xc, xk, y):
+    """The condition scale of a normal node's posterior mean: (kappa0 |m0| + sum_{i in R_v} |y_i|) / (kappa0 + n_v), with
+    the state before the update; one per node (the prior's |m0| where no row passes)."""
+    rows, y = node_rows(flat, dim_cont, xc, xk), np.asarray(y, dtype=np.float64)
+    post = np.asarray(state["post"], dtype=np.float64)
+    out = np.abs(post[:, 0]).copy()
+    for v, r in enumerate(rows):
+        if r is not None:
+            out[v] = (post[v, 1] * abs(post[v, 0]) + math.fsum(np.abs(y[r]))) / (post[v, 1] + int(r.sum()))
+    return out
+
+
+# columns of ``post`` that hold integer values (or halves): they must be bit-equal to the exact state
+INT_COLS = {BERNOULLI: (0, 1), POISSON: (0, 1), EXPONENTIAL: (0,), NORMAL: (1, 2, 4)}
+
+
+def node_errs(fam, got, want, scales=None):
+    """Deviations of a ``post`` table per node and per column, [nodes, P].  Integer-valued columns (bernoulli / categorical
+    counts, poisson alpha and beta, exponential alpha, normal kappa, alpha and n): 0 where bit-equal, inf elsewhere.
+    Columns made of non-negative terms (exponential beta, poisson sum ln y!, normal beta): |d| / |exact|.  Normal m:
+    |d| / scales[node] (``m_scales``).  A NaN, or an entry that differs where the scale is 0, is inf."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    if got.shape != want.shape:
+        raise ValueError("shapes differ")
+    out = np.zeros(want.shape)
+    ints = range(want.shape[1]) if fam == CATEGORICAL else INT_COLS[fam]
+    for c in range(want.shape[1]):
+        d = np.abs(got[:, c] - want[:, c])
+        if c in ints:
+            out[:, c] = np.where(got[:, c] == want[:, c], 0.0, np.inf)
+            continue
+        den = np.abs(want[:, c]) if not (fam == NORMAL and c == 0) else np.asarray(scales, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[:, c] = np.where(d == 0, 0.0, np.where(den > 0, d / den, np.inf))
+        out[np.isnan(d), c] = np.inf
+    return out
+
+
+def real_cols(fam):
+    return [] if fam in (BERNOULLI, CATEGORICAL) else [c for c in range({POISSON: 3, EXPONENTIAL: 2, NORMAL: 5}[fam])
+                                                       if c not in INT_COLS[fam]]
+
+
+def post_bounds(fam, plain, exact, scales=None):
+    """col -> 4 x e_plain + 64 eps for every real column, e_plain = max over nodes of node_errs(plain, exact)."""
+    e = node_errs(fam, plain, exact, scales)
+    return {c: 4 * float(e[:, c].max()) + 64 * EPS for c in real_cols(fam)}
+
+
+def predict_ld(flat, state, fam, degree, dim_cont, xc, xk, mode):
+    """``predict``'s fold in np.longdouble (mean, proba or var), [n] or [n, C] longdouble.  NaN node values (exponential
+    alpha <= 1, normal nu <= 2) follow ``node_values``."""
+    ld = np.longdouble
+    paths = route(flat, dim_cont, xc, xk)
+    post, g, prob = (np.asarray(state[k], dtype=np.float64).astype(ld) for k in ("post", "g", "prob"))
+    one = ld(1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if fam == BERNOULLI:
+            th = post[:, 0] / (post[:, 0] + post[:, 1])
+            V = np.stack([one - th, th], axis=1)
+        elif fam == CATEGORICAL:
+            V = post / post.sum(axis=1, keepdims=True)
+        elif fam == POISSON:
+            V = (post[:, 0] / post[:, 1])[:, None]          # alpha theta / (1 - theta), theta = 1 / (1 + beta)
+        elif fam == EXPONENTIAL:
+            V = np.where(post[:, 0] > 1, post[:, 1] / (post[:, 0] - one), ld(np.nan))[:, None]
+        else:
+            V = post[:, 0:1]
+            nu, lam = 2 * post[:, 2], post[:, 1] / (post[:, 1] + one) * post[:, 2] / post[:, 3]
+            S2 = np.where(nu > 2, nu / lam / (nu - 2), ld(np.nan))
+    B, n = paths.shape[0], paths.shape[1]
+    if mode == "var":
+        means, vars_ = np.zeros((B, n), dtype=ld), np.zeros((B, n), dtype=ld)
+        for b in range(B):
+            m, s2 = np.zeros(n, dtype=ld), np.zeros(n, dtype=ld)
+            D1 = paths.shape[2]
+            for j in range(D1 - 1, -1, -1):
+                v = paths[b][:, j]
+                valid = v >= 0
+                last = valid & ((paths[b][:, j + 1] < 0) if j + 1 < D1 else True)
+                m[last], s2[last] = V[v[last], 0], S2[v[last]]
+                mid = valid & ~last
+                gv, mv, vv = g[v[mid]], V[v[mid], 0], S2[v[mid]]
+                mm = (one - gv) * mv + gv * m[mid]
+                s2[mid] = (one - gv) * ((mm - mv) ** 2 + vv) + gv * ((mm - m[mid]) ** 2 + s2[mid])
+                m[mid] = mm
+            means[b], vars_[b] = m, s2
+        mix = prob @ means
+        return prob @ ((means - mix) ** 2 + vars_)
+    out = np.zeros((n, V.shape[1]), dtype=ld)
+    for b in range(B):
+        D1 = paths.shape[2]
+        val = np.zeros((n, V.shape[1]), dtype=ld)
+        for j in range(D1 - 1, -1, -1):
+            v = paths[b][:, j]
+            valid = v >= 0
+            last = valid & ((paths[b][:, j + 1] < 0) if j + 1 < D1 else True)
+            val[last] = V[v[last]]
+            mid = valid & ~last
+            gm = g[v[mid]][:, None]
+            val[mid] = (one - gm) * V[v[mid]] + gm * val[mid]
+        out += prob[b] * val
+    return out[:, 0] if mode == "mean" else out
+
+
+def entry_err(a, ref):
+    """|a - ref| / |ref| per entry (0 where equal, inf where the NaN patterns differ or ref = 0 and a does not)."""
+    a, ref = np.asarray(a, dtype=np.longdouble), np.asarray(ref, dtype=np.longdouble)
+    d = np.abs(a - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(d == 0, 0, np.where(np.abs(ref) > 0, d / np.abs(ref), np.inf))
+    e = np.where(np.isnan(a) & np.isnan(ref), 0, e)
+    e = np.where(np.isnan(a) != np.isnan(ref), np.inf, e)
+    return e.astype(np.float64)
+
+
 # ---- read-outs (plain float64, in the scalar learners' order of operations) ---------------------------------------------------
 def node_values(fam, degree, post, var=False):
     """V[nodes, C] (and the variance table for normal with ``var``)."""

@@ -105,12 +105,14 @@ def _binary_tree(depth, n_trees=1):
     return _mtree.FlatForest(i32(tree_off), i32(feat), i32(child0), i32(nchild), i32(thr_off), i32(dep), np.array(thr))
 
 
-H0 = {orc.BERNOULLI: [0.5, 0.5], orc.POISSON: [1.0, 1.0, 0.0], orc.EXPONENTIAL: [1.0, 1.0], orc.NORMAL: [0.0, 1.0, 1.0, 1.0, 0.0]}
+H0 = {orc.BERNOULLI: [0.5, 0.5], orc.CATEGORICAL: [0.5, 0.5, 0.5], orc.POISSON: [1.0, 1.0, 0.0], orc.EXPONENTIAL: [1.0, 1.0],
+      orc.NORMAL: [0.0, 1.0, 1.0, 1.0, 0.0]}
+DEGREE = {orc.CATEGORICAL: 3}
 
 
 def _engine(flat, fam, g0=0.5):
     from bayesml_amd import _mtree
-    eng = _mtree.MtreePass(flat, fam, 0, 1, 0, [], H0[fam], torch.device("cuda", 0))
+    eng = _mtree.MtreePass(flat, fam, DEGREE.get(fam, 0), 1, 0, [], H0[fam], torch.device("cuda", 0))
     st = dict(g=np.where(flat.feat < 0, 0.0, g0), post=np.tile(H0[fam], (flat.n_nodes, 1)), lml=np.full(flat.n_nodes, np.nan),
               lcm=np.zeros(flat.n_nodes), prob=np.ones(flat.n_trees) / flat.n_trees)
     eng.set_state(st)
@@ -120,6 +122,8 @@ def _engine(flat, fam, g0=0.5):
 def _sample(fam, x, rng):
     if fam == orc.BERNOULLI:
         return (rng.random(len(x)) < x).astype(np.int64)
+    if fam == orc.CATEGORICAL:
+        return (np.floor(x * 8).astype(np.int64) + rng.integers(0, 2, len(x))) % 3
     if fam == orc.POISSON:
         return rng.poisson(1 + 5 * x)
     if fam == orc.EXPONENTIAL:
@@ -131,7 +135,7 @@ def _lml_scale(fam, post):
     """The largest term of the family's log marginal likelihood over the nodes."""
     from scipy.special import gammaln
     a = np.abs(post)
-    if fam == orc.BERNOULLI:
+    if fam in (orc.BERNOULLI, orc.CATEGORICAL):
         return float(np.max(gammaln(a.sum(1) + 1)))
     if fam == orc.NORMAL:
         return float(np.max(np.abs(post[:, 2] * np.log(post[:, 3])) + gammaln(post[:, 2]) + post[:, 4]))
@@ -144,9 +148,17 @@ def _against_oracle(flat, fam, x, y, what):
     n, bad = eng.update(xc, None, eng.adopt_y(y))
     assert (n, bad) == (len(x), 0)
     got = eng.get_state()
-    want, counts = orc.batch_update(flat.arrays(), st, fam, 0, H0[fam], 1, x[:, None], None, y)
+    args = (flat.arrays(), st, fam, DEGREE.get(fam, 0), H0[fam], 1, x[:, None], None, y)
+    want, counts = orc.batch_update(*args)
     si, _ = eng.last_stats()
     assert np.array_equal(si[:, 0], counts), what
+    # per node and per column: integer-valued columns exactly, real ones against the reference's own per-node float64 form
+    scales = orc.m_scales(flat.arrays(), st, 1, x[:, None], None, y) if fam == orc.NORMAL else None
+    node, bound = orc.node_errs(fam, got["post"], want["post"], scales), orc.post_bounds(fam, orc.plain_update(*args)["post"],
+                                                                                         want["post"], scales)
+    for c in range(node.shape[1]):
+        print(f"{what}: post[:, {c}] {node[:, c].max():.3e}, bound {bound.get(c, 0.0):.3e}")
+        assert node[:, c].max() <= bound.get(c, 0.0), (what, c)
     errs = orc.state_errs(got, want)
     seen = ~np.isnan(want["lml"])
     scale = _lml_scale(fam, want["post"][seen])
@@ -161,7 +173,7 @@ def _against_oracle(flat, fam, x, y, what):
     return eng
 
 
-@pytest.mark.parametrize("fam", [orc.BERNOULLI, orc.POISSON, orc.EXPONENTIAL, orc.NORMAL])
+@pytest.mark.parametrize("fam", [orc.BERNOULLI, orc.CATEGORICAL, orc.POISSON, orc.EXPONENTIAL, orc.NORMAL])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1025])
 def test_reduction_edges(fam, n):
     """Wave and slab edges of the reduction: N = 63, 64, 65, and one slab of 1024 rows plus one row."""

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fake_metatree_engine as fk
+import metatree_edge_cases as ec
 import metatree_oracle as orc
 from conftest import GOLDEN, load_golden
 
@@ -362,3 +363,201 @@ def test_there_is_no_cpu_fallback():
     inp = orc.case_inputs(CASE["threeway"])
     with pytest.raises(EngineUnavailableError):
         m.update_posterior(inp["xc1"], inp["xk1"], inp["y1"], alg_type="given_MT")
+
+
+# ---- the yardsticks of tests/test_gpu_metatree_edges.py, pinned without a GPU ------------------------------------------------
+def _fixture_start(name):
+    fx, case = load_golden(f"metatree_{name}.npz"), CASE[name]
+    fam, dc = orc.FAMILY[case["sub"]], case["consts"]["c_dim_continuous"]
+    degree = case.get("sub_constants", {}).get("c_degree", 0)
+    h0 = orc.post_of(fam, _subs()[case["sub"]].LearnModel(**case.get("sub_constants", {})))
+    flat = {k: fx[k] for k in orc.STRUCT}
+    n = len(flat["feat"])
+    st = dict(g=fx["init_g"], post=np.tile(h0, (n, 1)), lml=np.full(n, np.nan), lcm=np.zeros(n), prob=fx["init_prob"])
+    return fx, flat, st, fam, degree, h0, dc
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_plain_update_is_the_references_arithmetic(name):
+    """``plain_update`` (per node, float64 numpy) reproduces the reference's own first-stage state within 64 eps in the
+    existing metrics, and ``node_errs`` of a state against itself is 0."""
+    fx, flat, st, fam, degree, h0, dc = _fixture_start(name)
+    plain = orc.plain_update(flat, st, fam, degree, h0, dc, fx["xc1"], fx["xk1"], fx["y1"])
+    errs = orc.state_errs(plain, {k: fx[f"after1_{k}"] for k in orc.STATE})
+    assert max(errs.values()) <= 64 * EPS and orc.rel_err(plain["lcm"], fx["after1_lcm"]) <= 64 * EPS, errs
+    scales = orc.m_scales(flat, st, dc, fx["xc1"], fx["xk1"], fx["y1"]) if fam == orc.NORMAL else None
+    assert not orc.node_errs(fam, fx["after1_post"], fx["after1_post"], scales).any()
+    # the fixture's own state is within 4 x e_plain + 64 eps of the exact one, per node and column (it IS the plain form)
+    exact, _ = orc.batch_update(flat, st, fam, degree, h0, dc, fx["xc1"], fx["xk1"], fx["y1"])
+    e, bound = orc.node_errs(fam, fx["after1_post"], exact["post"], scales), orc.post_bounds(fam, plain["post"], exact["post"], scales)
+    for c in range(e.shape[1]):
+        assert e[:, c].max() <= bound.get(c, 0.0), (c, e[:, c].max())
+
+
+def test_node_errs_sees_one_small_node_beside_a_large_one():
+    """What the array-wide metric hides: a level of 1e6 in one node's m allows 1e-8 on every beta; per node it does not."""
+    want = np.array([[1e6, 11.0, 6.0, 3.0, 10.0], [0.5, 3.0, 2.0, 1e-3, 2.0]])
+    got = want.copy()
+    got[1, 3] += 1e-9
+    assert orc.rel_err(got, want) <= 64 * EPS
+    e = orc.node_errs(orc.NORMAL, got, want, scales=[1e6, 0.5])
+    assert e[1, 3] > 1e-7 and e[0].max() == 0 and e[1, [0, 1, 2, 4]].max() == 0
+    got[0, 1] = np.nextafter(11.0, 12.0)
+    assert np.isinf(orc.node_errs(orc.NORMAL, got, want, scales=[1e6, 0.5])[0, 1])
+    got = want.copy()
+    got[0, 0] += 1e-6
+    assert orc.node_errs(orc.NORMAL, got, want, scales=[1e6, 0.5])[0, 0] == pytest.approx(1e-12, rel=1e-3)
+
+
+def test_predict_ld_agrees_with_predict():
+    """The long-double fold rounded to float64 agrees with the float64 oracle to a few eps on the fixtures' states: e64, the
+    unit of the prediction bounds, is the float64 fold's own rounding and nothing else."""
+    for name, mode in (("bernoulli", "proba"), ("poisson", "mean"), ("normal", "var")):
+        fx, flat, _, fam, degree, _, dc = _fixture_start(name)
+        st = {k: fx[f"after2_{k}"] for k in orc.STATE}
+        f64 = orc.predict(flat, st, fam, degree, dc, fx["xcp"], fx["xkp"], mode)
+        ld = orc.predict_ld(flat, st, fam, degree, dc, fx["xcp"], fx["xkp"], mode)
+        assert ld.dtype == np.longdouble and ld.shape == f64.shape
+        e64 = orc.entry_err(f64, ld)
+        assert e64.max() <= (64 if mode != "var" else 4096) * EPS, (name, e64.max())
+        assert np.all(np.abs(ld.astype(np.float64) - f64) <= e64 * np.abs(f64) + np.spacing(f64))
+
+
+def _exact(case, state=None):
+    return orc.batch_update(case["tabs"], case["state"] if state is None else state, case["fam"], case["degree"], case["h0"],
+                            case["dim_cont"], case["xc"], case["xk"], case["y"])
+
+
+def _inner_seen(case, want):
+    return (case["tabs"]["feat"] >= 0) & ~np.isnan(want["lml"])
+
+
+def test_edge_cases_reach_what_they_name():
+    """Every claim of tests/metatree_edge_cases.py, so that no GPU test passes on a case that misses its branch."""
+    from bayesml_amd import _mtree
+    assert (ec.LDS_SLOTS, ec.MAX_SLABS, ec.MIN_SPAN) == (_mtree.LDS_SLOTS, _mtree.MAX_SLABS, _mtree.MIN_SPAN)
+    # conditioning (post alone is judged there): the recipes hold what their names say
+    for kind in ec.CONDITIONING:
+        for fam in (orc.NORMAL, orc.EXPONENTIAL):
+            for seed, n in ((0, 200), (1, 200), (10, 50), (11, 50)):
+                case = ec.conditioning(kind, fam, n=n, seed=seed)
+                leaf = case["claims"]["leaf"]
+                assert (case["y"] > 0).all() or fam == orc.NORMAL
+                if kind.startswith("outlier"):
+                    assert (leaf == 0).sum() == 1 and leaf[0] == 0 and case["y"][0] == float(kind.split("_")[1])
+                    assert np.all(np.abs(case["y"][1:] - 1e-3) < 1e-3)
+                if kind == "constant":
+                    assert (leaf == 3).sum() >= 3 and len(set(case["y"][leaf == 3])) == 1
+                if kind == "scales" and n == 200:
+                    assert len(set(leaf)) == 8 and case["y"].max() / np.abs(case["y"]).min() > 1e20
+        _, counts = _exact(ec.conditioning(kind, orc.NORMAL))
+        assert counts[0] == 200 and (counts[:7] > 0).all()
+    # own rows at inner nodes
+    for fam in (orc.NORMAL, orc.EXPONENTIAL, orc.POISSON):
+        case = ec.nan_rows(fam)
+        want, counts = _exact(case)
+        assert case["claims"]["own_root"] > 0 and case["claims"]["own_d1"] > 0
+        assert counts[0] - counts[1] - counts[2] == case["claims"]["own_root"]
+        assert counts[1] - counts[3] - counts[4] > 0 and counts[2] - counts[5] - counts[6] > 0
+        inner = _inner_seen(case, want)
+        # (the root's children do not hold its own rows, so their L sum is far above its lml and its h_g ends next to 1)
+        assert inner.sum() == 7 and np.all((want["g"][1:7] > 0) & (want["g"][1:7] < 1)) and want["g"][0] > 0.5
+    # the mixture: t = ln(1 - g0) + lml - ln g0 - sum L of node 1 is beyond exp's range for every g0 inside (0, 1)
+    mp = orc.mp
+    for fam in (orc.BERNOULLI, orc.NORMAL):
+        for sign in (-1, 1):
+            want, _ = _exact(ec.mixture(fam, 0.5, sign))
+            gap = mp.mpf(float(want["lml"][1])) - mp.mpf(float(want["lcm"][3])) - mp.mpf(float(want["lcm"][4]))
+            for g0 in ec.G0[2:]:
+                t = mp.log(1 - mp.mpf(g0)) - mp.log(mp.mpf(g0)) + gap
+                assert sign * t > 1000, (fam, sign, g0, t)
+            assert want["prob"][1] == 0.0 and want["prob"][2] == 0.0 and 1e-3 < want["prob"][3] < 0.999
+    assert len(set(ec.G0)) == 7 and {0.0, 1.0, 5e-324, 1e-300, 2.0 ** -53, 0.5, 1.0 - 2.0 ** -53} == set(ec.G0)
+    # limits
+    case = ec.wide_continuous()
+    paths = orc.route(case["tabs"], 1, case["xc"], None)
+    stops = orc.stops(paths)[0]
+    assert set(stops) == set(range(17)) and (stops == 0).sum() == 1           # every child, and the NaN row at the root
+    x = case["xc"][:, 0]
+    assert np.array_equal(stops[:17], np.minimum(np.arange(17), 15) + 1) and stops[x == -np.inf] == 1 and stops[x == np.inf] == 16
+    assert np.array_equal(case["xc"].astype(np.float32).astype(np.float64), case["xc"], equal_nan=True)
+    for card in (16, 20):
+        case = ec.wide_categorical(card)
+        assert case["claims"]["outside"] == (0 if card == 16 else (case["xk"] >= 16).sum()) and set(case["xk"][:, 0]) == set(range(card))
+    for fam, degree, n_nodes, lds in ((orc.CATEGORICAL, 16, 361, True), (orc.CATEGORICAL, 16, 362, False),
+                                      (orc.POISSON, 0, 2048, True), (orc.POISSON, 0, 2049, False)):
+        case = ec.lds_edge(fam, n_nodes, degree)
+        tabs = case["tabs"]
+        slots = n_nodes * case["claims"]["cols"]
+        assert len(tabs["feat"]) == n_nodes and case["claims"]["lds"] == lds == (slots <= _mtree.LDS_SLOTS)
+        assert slots == {361: 6137, 362: 6154, 2048: 6144, 2049: 6147}[n_nodes]
+        assert np.all(np.diff(tabs["depth"]) >= 0) and np.all(tabs["child0"][tabs["feat"] >= 0] > np.flatnonzero(tabs["feat"] >= 0))
+        assert (orc.stops(orc.route(tabs, 1, case["xc"], None))[0] == n_nodes - 1).sum() >= 40
+        _mtree.check_limits(1, n_nodes, 2, int(tabs["depth"].max()), degree)
+    for fam in (orc.BERNOULLI, orc.NORMAL):
+        case = ec.deep_chain(fam)
+        tabs = case["tabs"]
+        assert len(tabs["feat"]) == 49 and tabs["depth"].max() == 24
+        paths = orc.route(tabs, 1, case["xc"], None)
+        assert (paths[0, :, 24] == 48).sum() == case["claims"]["deepest"] >= 5 and len(set(orc.stops(paths)[0])) >= 20
+    case = ec.many_trees()
+    assert len(case["tabs"]["tree_off"]) == 1025 and len(case["y"]) == 257
+    # the global-scratch rewrite: four leaves, every round of 64 rows holds all four, and the lead lane of a leaf moves
+    for fam in (orc.POISSON, orc.NORMAL):
+        case = ec.rewrite(fam)
+        ni, nr, _ = _mtree.stat_cols(fam)
+        assert len(case["tabs"]["feat"]) * (ni + min(nr, 1)) > _mtree.LDS_SLOTS and len(case["tabs"]["feat"]) * 2 > _mtree.LDS_SLOTS
+        stops = orc.stops(orc.route(case["tabs"], 2, case["xc"], None))[0]
+        leaves = [v for v in set(stops) if case["tabs"]["feat"][v] < 0]
+        assert len(leaves) == 4 and (stops == 0).sum() > 100 and ((stops == 1) | (stops == 2)).sum() > 100
+        first = [[int(np.flatnonzero(stops[r * 64:(r + 1) * 64] == v)[0]) for v in leaves] for r in range(8)]
+        assert all(len(set(col)) >= 3 for col in zip(*first))
+    # slabs
+    assert _mtree.slabs_for(65537, 7, 2) == 64
+    spans = ec.slab_spans(65537, 64)
+    assert spans[0] == (0, 1088) and spans[60] == (65280, 65537) and spans[61:] == [(s * 1088, s * 1088) for s in (61, 62, 63)]
+    spans = ec.slab_spans(65, 64)
+    assert spans[:2] == [(0, 64), (64, 65)] and all(lo == hi for lo, hi in spans[2:])
+    assert ec.slab_spans(5000, 1) == [(0, 5000)] and _mtree.slabs_for(5000, 7, 2) == 5 and _mtree.slabs_for(65, 7, 2) == 1
+
+
+@pytest.mark.parametrize("fam,degree", [(orc.BERNOULLI, 0), (orc.CATEGORICAL, 16), (orc.CATEGORICAL, 3), (orc.POISSON, 0),
+                                        (orc.EXPONENTIAL, 0), (orc.NORMAL, 0)])
+def test_predict_cases_reach_what_they_name(fam, degree):
+    """Rows stop at inner nodes, h_g = 0 and 1 lie on walked paths, a tree has probability 0, the NaN values occur in some
+    rows and not in all, and the oracle alone has a clear margin in at least 90 % of the rows of a class test."""
+    for n in (1, 255, 256, 257):
+        case = ec.predict_case(fam, n, degree)
+        tabs, st = case["tabs"], case["state"]
+        assert (st["prob"] == 0).sum() == 1 and st["prob"].sum() == 1.0
+        paths = orc.route(tabs, 2, case["xc"], None)
+        if n < 255:
+            continue
+        stops = orc.stops(paths)
+        assert (tabs["feat"][stops] >= 0).any(axis=1).all()          # in every tree some row stops at an inner node
+        walked = np.unique(paths[paths >= 0])
+        inner = walked[tabs["feat"][walked] >= 0]
+        assert (st["g"][inner] == 0).any() and (st["g"][inner] == 1).any() and ((st["g"][inner] > 0) & (st["g"][inner] < 1)).any()
+        a = (tabs, st, fam, degree, 2, case["xc"], None)
+        if fam in (orc.BERNOULLI, orc.CATEGORICAL):
+            f64, ld = orc.predict(*a, "proba"), orc.predict_ld(*a, "proba")
+            bound = 4 * orc.entry_err(f64, ld) + 64 * EPS
+            top = np.sort(f64, axis=1)
+            assert (top[:, -1] - top[:, -2] > 2 * bound.max(axis=1) * top[:, -1]).mean() >= 0.9
+        if fam in (orc.EXPONENTIAL, orc.NORMAL):
+            want = orc.predict(*a, "mean" if fam == orc.EXPONENTIAL else "var")
+            assert 0 < np.isnan(want).sum() < n
+    sym = ec.predict_case(orc.BERNOULLI, 257, symmetric=True)
+    proba = orc.predict(sym["tabs"], sym["state"], orc.BERNOULLI, 0, 2, sym["xc"], None, "proba")
+    assert np.array_equal(proba[:, 0], proba[:, 1])
+
+
+def test_one_past_a_limit_is_refused_without_a_gpu():
+    from bayesml_amd import _mtree
+    from bayesml_amd._engine import EngineLimitError
+    for tabs in (ec.chain(25), ec.stumps(1025)):
+        with pytest.raises(EngineLimitError, match="bayesml itself has no such limit"):
+            _mtree.MtreePass(_mtree.FlatForest(**tabs), orc.BERNOULLI, 0, 1, 0, [], [0.5, 0.5])
+    for tabs in (ec.chain(24), ec.stumps(1024)):
+        flat = _mtree.FlatForest(**tabs)
+        _mtree.check_limits(flat.n_trees, flat.max_tree_nodes, flat.max_children, flat.max_depth)

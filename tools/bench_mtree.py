@@ -99,17 +99,16 @@ def main():
                      lcm=np.zeros(flat.n_nodes), prob=np.ones(flat.n_trees) / flat.n_trees)
         eng.set_state(start)
         y = eng.adopt_y(ys[name])
-        pivot = y[:1].clone() if fam == _mtree.NORMAL else None
         stop = eng.route(xd, None)[0]
         row = dict(sub_model=name, n=args.n, trees=args.trees, depth=args.depth, nodes=flat.n_nodes)
         row["route_ms"] = round(timed(lambda: eng.route(xd, None), args.reps, args.warmup), 4)
-        row["reduce_ms"] = round(timed(lambda: eng.reduce(stop, y, pivot), args.reps, args.warmup), 4)
-        row["sweep_ms"] = round(timed(lambda: eng.sweep(pivot), args.reps, args.warmup), 4)
+        row["reduce_ms"] = round(timed(lambda: eng.reduce(stop, y), args.reps, args.warmup), 4)
+        row["sweep_ms"] = round(timed(lambda: eng.sweep(), args.reps, args.warmup), 4)
         eng.set_state(start)
 
         def update():
-            eng.reduce(eng.route(xd, None)[0], y, pivot)
-            eng.sweep(pivot)
+            eng.reduce(eng.route(xd, None)[0], y)
+            eng.sweep()
         row["update_ms"] = round(timed(update, args.reps, args.warmup), 4)
         row["predict_ms"] = round(timed(lambda: eng.predict(xd, None, mode), args.reps, args.warmup), 4)
         row["route_gbs"] = round((x.nbytes + 4 * args.n * args.trees) / row["route_ms"] / 1e6, 1)
