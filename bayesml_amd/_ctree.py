@@ -17,7 +17,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._engine import EngineError, EngineLimitError, EngineUnavailableError, _STATUS, load_library as _load_gmmvb
+from ._engine import EngineLimitError
+from ._native import PLOT_MSG, bind, gpu_device, stream_ptr  # noqa: F401  (PLOT_MSG: the model package reads it here)
 from ._expfam import adopt_tensor
 
 U8, I32, I64 = range(3)                  # enum ctree_dtype
@@ -37,20 +38,7 @@ SYMBOLS = {
 }
 _CODES = {torch.uint8: U8, torch.int32: I32, torch.int64: I64}
 
-_declared = False
-
-
-def load_library() -> ctypes.CDLL:
-    """The in-tree library with the ctree_* prototypes declared (works without a GPU)."""
-    global _declared
-    lib = _load_gmmvb()
-    if not _declared:
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        _declared = True
-    return lib
+load_library, _check = bind("ctree", SYMBOLS)
 
 
 def check_limit(c_k: int, c_d_max: int):
@@ -69,23 +57,13 @@ def offsets(k: int, D: int):
     return off
 
 
-def _check(lib, rc, what):
-    if rc != 0:
-        msg = lib.ctree_last_error()
-        raise EngineError(f"{what}: {_STATUS.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-
 class CtreePass:
     """The tables of one context tree on one device and the three entry points on them."""
 
     def __init__(self, k: int, D: int, device=None):
         self.lib = load_library()
         check_limit(k, D)
-        if not torch.cuda.is_available():
-            raise EngineUnavailableError("bayesml_amd's context-tree engine needs an MI355X: there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise EngineUnavailableError(f"device {self.device} is not a GPU: there is no CPU fallback")
+        self.device = gpu_device(device, "context-tree engine")
         self.k, self.D, self.off = int(k), int(D), offsets(k, D)
         self.nodes = self.off[-1]
         assert self.nodes == self.lib.ctree_table_len(self.k, self.D, -1)
@@ -98,9 +76,6 @@ class CtreePass:
         self._out = torch.empty(2 + self.k ** (self.D + 1), dtype=torch.int64, device=dev)
         self.launch_info = ""
 
-    def _stream(self):
-        return _vp(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- the sample -----------------------------------------------------------------------------------------------------
     def adopt(self, x):
         return adopt_tensor(x, self.device, "i")
@@ -112,8 +87,8 @@ class CtreePass:
         """``[n | bad | cnt_D[k^D][k]]`` of the adopted sample, int64 on the device (overwritten by the next call)."""
         with torch.cuda.device(self.device):
             rc = self.lib.ctree_count(_CODES[x.dtype], x.data_ptr(), x.shape[0], self.k, self.D, self._out.data_ptr(),
-                                      self._work.data_ptr(), self._stream())
-        _check(self.lib, rc, "ctree_count")
+                                      self._work.data_ptr(), stream_ptr(self.device))
+        _check(rc, "ctree_count")
         self.launch_info = "ctree_count"
         return self._out
 
@@ -127,8 +102,8 @@ class CtreePass:
         with torch.cuda.device(self.device):
             rc = self.lib.ctree_sweep(self.k, self.D, self._out.data_ptr() + 16, head.data_ptr(), n_head, self.beta.data_ptr(),
                                       self.g.data_ptr(), self.exists.data_ptr(), float(hn_g), hb.data_ptr(),
-                                      cl.data_ptr() if want_counts else None, self._work.data_ptr(), self._stream())
-        _check(self.lib, rc, "ctree_sweep")
+                                      cl.data_ptr() if want_counts else None, self._work.data_ptr(), stream_ptr(self.device))
+        _check(rc, "ctree_sweep")
         oD = self.off[self.D]
         self.leaf[oD:] = self.exists[oD:]         # a node at the maximal depth is a leaf from its creation on
         self.launch_info = "ctree_count + ctree_sweep"
@@ -146,8 +121,8 @@ class CtreePass:
         ml = torch.empty(self.nodes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             rc = self.lib.ctree_map(self.k, self.D, self.g.data_ptr(), self.exists.data_ptr(), float(hn_g), ml.data_ptr(),
-                                    self._work.data_ptr(), self._stream())
-        _check(self.lib, rc, "ctree_map")
+                                    self._work.data_ptr(), stream_ptr(self.device))
+        _check(rc, "ctree_map")
         self.launch_info = "ctree_map"
         return ml.cpu().numpy()
 
@@ -191,5 +166,3 @@ class CtreePass:
     def close(self):
         self._work = self._out = None
 
-
-PLOT_MSG = "plotting is out of scope for bayesml_amd (SURVEY.md section 2)"

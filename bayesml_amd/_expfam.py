@@ -13,7 +13,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._engine import EngineError, EngineLimitError, EngineUnavailableError, _STATUS, load_library as _load_gmmvb
+from ._engine import EngineError, EngineLimitError
+from ._native import PLOT_MSG, bind, gpu_device, stream_ptr  # noqa: F401  (PLOT_MSG: the model packages read it here)
 
 BERNOULLI, COUNTS, ONEHOT, POISSON, EXPONENTIAL, NORMAL = range(6)      # enum expfam_family
 U8, I32, I64, F32, F64 = range(5)                                      # enum expfam_dtype
@@ -37,20 +38,7 @@ _ENTRY = {BERNOULLI: "expfam_stats_bernoulli", COUNTS: "expfam_stats_counts", ON
           POISSON: "expfam_stats_poisson", EXPONENTIAL: "expfam_stats_exponential", NORMAL: "expfam_stats_normal"}
 _CODES = {torch.uint8: U8, torch.int32: I32, torch.int64: I64, torch.float32: F32, torch.float64: F64}
 
-_declared = False
-
-
-def load_library() -> ctypes.CDLL:
-    """The in-tree library with the expfam_* prototypes declared (works without a GPU)."""
-    global _declared
-    lib = _load_gmmvb()
-    if not _declared:
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        _declared = True
-    return lib
+load_library, _check = bind("expfam", SYMBOLS)
 
 
 def check_degree(c_degree: int, what: str):
@@ -59,12 +47,6 @@ def check_degree(c_degree: int, what: str):
     if c_degree > MAX_DEGREE:
         raise EngineLimitError(f"bayesml_amd.{what} supports at most {MAX_DEGREE} categories in this version "
                                f"(got {c_degree}); bayesml itself has no such limit")
-
-
-def _check(lib, rc, what):
-    if rc != 0:
-        msg = lib.expfam_last_error()
-        raise EngineError(f"{what}: {_STATUS.get(rc, rc)}: {msg.decode() if msg else ''}")
 
 
 def code(dtype):
@@ -126,11 +108,7 @@ class ExpfamPass:
 
     def __init__(self, device=None):
         self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise EngineUnavailableError("bayesml_amd's scalar conjugate data passes need an MI355X: there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise EngineUnavailableError(f"device {self.device} is not a GPU: there is no CPU fallback")
+        self.device = gpu_device(device, "scalar conjugate data passes")
         self._work = {}
         self.launch_info = ""
 
@@ -151,7 +129,7 @@ class ExpfamPass:
         out = torch.empty(n_slots, dtype=torch.int64, device=self.device)
         fn = getattr(self.lib, _ENTRY[family])
         with torch.cuda.device(self.device):
-            stream = _vp(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = stream_ptr(self.device)
             head = (code(x.dtype), x.data_ptr(), x.shape[0])
             if family == COUNTS:
                 rc = fn(*head, degree, out.data_ptr(), work.data_ptr(), stream)
@@ -160,7 +138,7 @@ class ExpfamPass:
                 rc = fn(*head, degree, ld, out.data_ptr(), work.data_ptr(), stream)
             else:
                 rc = fn(*head, out.data_ptr(), work.data_ptr(), stream)
-        _check(self.lib, rc, _ENTRY[family])
+        _check(rc, _ENTRY[family])
         self.launch_info = _ENTRY[family]
         return out
 
@@ -202,5 +180,3 @@ def is_array(x):
 def size_of(x):
     return int(x.numel()) if isinstance(x, torch.Tensor) else int(x.size)
 
-
-PLOT_MSG = "plotting is out of scope for bayesml_amd (SURVEY.md section 2)"

@@ -18,7 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._engine import EngineError, EngineLimitError, EngineUnavailableError, _STATUS, load_library as _load_gmmvb
+from ._engine import EngineLimitError
+from ._native import PLOT_MSG, bind, gpu_device, stream_ptr  # noqa: F401  (PLOT_MSG: the model package reads it here)
 from ._expfam import adopt_tensor
 
 U8, I32, I64, F32, F64 = range(5)                                  # enum mtree_dtype
@@ -48,26 +49,13 @@ SYMBOLS = {
     "mtree_stat_cols": (_int, [_int, _int, _ip, _ip, _ip]),
     "mtree_work_len": (_i64, [_i32, _int, _int, _int]),
     "mtree_route": (_int, [_fp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "mtree_reduce": (_int, [_fp, _int, _int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
-    "mtree_sweep": (_int, [_fp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mtree_reduce": (_int, [_fp, _int, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mtree_sweep": (_int, [_fp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mtree_predict": (_int, [_fp, _int, _int, _int, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 _CODES = {torch.uint8: U8, torch.int32: I32, torch.int64: I64, torch.float32: F32, torch.float64: F64}
 
-_declared = False
-
-
-def load_library() -> ctypes.CDLL:
-    """The in-tree library with the mtree_* prototypes declared (works without a GPU)."""
-    global _declared
-    lib = _load_gmmvb()
-    if not _declared:
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        _declared = True
-    return lib
+load_library, _check = bind("mtree", SYMBOLS)
 
 
 def stat_cols(family: int, degree: int = 0):
@@ -128,12 +116,6 @@ def slabs_for(n: int, n_nodes: int, cols: int) -> int:
     return int(max(1, min(MAX_SLABS, -(-n // MIN_SPAN), WORK_SLOTS // max(1, n_nodes * cols))))
 
 
-def _check(lib, rc, what):
-    if rc != 0:
-        msg = lib.mtree_last_error()
-        raise EngineError(f"{what}: {_STATUS.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-
 def _ptr(t):
     return None if t is None or t.numel() == 0 else t.data_ptr()
 
@@ -144,11 +126,7 @@ class MtreePass:
     def __init__(self, flat: FlatForest, family: int, degree: int, dim_cont: int, dim_cat: int, cat_card, h0, device=None):
         self.lib = load_library()
         check_limits(flat.n_trees, flat.max_tree_nodes, flat.max_children, flat.max_depth, degree)
-        if not torch.cuda.is_available():
-            raise EngineUnavailableError("bayesml_amd's meta-tree engine needs an MI355X: there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise EngineUnavailableError(f"device {self.device} is not a GPU: there is no CPU fallback")
+        self.device = gpu_device(device, "meta-tree engine")
         self.flat, self.family, self.degree = flat, int(family), int(degree)
         self.dim_cont, self.dim_cat = int(dim_cont), int(dim_cat)
         self.ni, self.nr, self.np_ = stat_cols(self.family, self.degree)
@@ -174,9 +152,6 @@ class MtreePass:
                                    self.dim_cont, self.dim_cat, *(_ptr(self._tabs[k]) for k in
                                                                   ("tree_off", "feat", "child0", "nchild", "thr_off", "depth", "thr")))
         self.launch_info = ""
-
-    def _stream(self):
-        return _vp(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- the sample -----------------------------------------------------------------------------------------------------
     def adopt_x(self, x_continuous, x_categorical):
@@ -208,8 +183,8 @@ class MtreePass:
         cc, ck = self._codes(xc, xk)
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_route(ctypes.byref(self.struct), cc, _ptr(xc), ck, _ptr(xk), _ptr(self.cat_card), n,
-                                      stop.data_ptr(), _ptr(path), self._bad.data_ptr(), self._stream())
-        _check(self.lib, rc, "mtree_route")
+                                      stop.data_ptr(), _ptr(path), self._bad.data_ptr(), stream_ptr(self.device))
+        _check(rc, "mtree_route")
         return stop, path, self._bad
 
     def _scratch(self, S):
@@ -224,18 +199,19 @@ class MtreePass:
         work = self._scratch(S)
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_reduce(ctypes.byref(self.struct), self.family, self.degree, stop.data_ptr(), y.data_ptr(),
-                                       None, n, S, self.stat_int.data_ptr(), self.stat_real.data_ptr(), work.data_ptr(), self._stream())
-        _check(self.lib, rc, "mtree_reduce")
+                                       n, S, self.stat_int.data_ptr(), self.stat_real.data_ptr(), work.data_ptr(),
+                                       stream_ptr(self.device))
+        _check(rc, "mtree_reduce")
 
     def sweep(self):
         work = self._scratch(1)
         lnp = torch.log(self.prob)
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_sweep(ctypes.byref(self.struct), self.family, self.degree, self.stat_int.data_ptr(),
-                                      self.stat_real.data_ptr(), None, self.h0.data_ptr(), self.post.data_ptr(),
+                                      self.stat_real.data_ptr(), self.h0.data_ptr(), self.post.data_ptr(),
                                       self.g.data_ptr(), self.lml.data_ptr(), self.lcm.data_ptr(), lnp.data_ptr(), work.data_ptr(),
-                                      self._stream())
-        _check(self.lib, rc, "mtree_sweep")
+                                      stream_ptr(self.device))
+        _check(rc, "mtree_sweep")
         p = torch.exp(lnp - lnp.max())
         self.prob.copy_(p / p.sum())
 
@@ -260,8 +236,8 @@ class MtreePass:
         with torch.cuda.device(self.device):
             rc = self.lib.mtree_predict(ctypes.byref(self.struct), self.family, self.degree, mode, cc, _ptr(xc), ck, _ptr(xk),
                                         n, self.post.data_ptr(), self.g.data_ptr(), self.prob.data_ptr(),
-                                        self._values.data_ptr(), out.data_ptr(), self._stream())
-        _check(self.lib, rc, "mtree_predict")
+                                        self._values.data_ptr(), out.data_ptr(), stream_ptr(self.device))
+        _check(rc, "mtree_predict")
         self.launch_info = "mtree_predict"
         return out.cpu().numpy()
 
@@ -285,5 +261,3 @@ class MtreePass:
     def close(self):
         self._work = None
 
-
-PLOT_MSG = "plotting is out of scope for bayesml_amd (SURVEY.md section 2)"

@@ -14,9 +14,9 @@ import numpy as np
 
 from . import _check
 from ._exceptions import CriteriaError, ParameterFormatError
+from ._native import PLOT_MSG  # noqa: F401  (the two model packages read it here)
 
 _LOSS_MSG = "Unsupported loss function! This function supports \"squared\", \"0-1\", \"abs\", and \"KL\"."
-PLOT_MSG = "plotting is out of scope for bayesml_amd (SURVEY.md section 2)"
 
 
 def init_params(obj, prefixes, D):

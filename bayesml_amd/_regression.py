@@ -11,7 +11,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._engine import EngineError, EngineLimitError, EngineUnavailableError, _STATUS, load_library as _load_gmmvb
+from ._engine import EngineLimitError
+from ._native import bind, gpu_device, stream_ptr
 
 REGVB_F32, REGVB_F64 = 0, 1
 PAD_NONE, PAD_ZEROS = 0, 1
@@ -30,20 +31,7 @@ SYMBOLS = {
     "regvb_predict": (_int, [_int, _int, _vp, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
-_declared = False
-
-
-def load_library() -> ctypes.CDLL:
-    """The in-tree library with the regvb_* prototypes declared (works without a GPU)."""
-    global _declared
-    lib = _load_gmmvb()
-    if not _declared:
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        _declared = True
-    return lib
+load_library, _check = bind("regvb", SYMBOLS)
 
 
 def check_features(n_features: int, what: str):
@@ -52,12 +40,6 @@ def check_features(n_features: int, what: str):
     if n_features > MAX_FEATURES:
         raise EngineLimitError(f"bayesml_amd.{what} supports at most {MAX_FEATURES} regression coefficients in this "
                                f"version (got {n_features}); bayesml itself has no such limit")
-
-
-def _check(lib, rc, what):
-    if rc != 0:
-        msg = lib.regvb_last_error()
-        raise EngineError(f"{what}: {_STATUS.get(rc, rc)}: {msg.decode() if msg else ''}")
 
 
 def _code(dtype):
@@ -93,18 +75,11 @@ class RegressionPass:
         check_features(D, "regression")
         self.D = int(D)
         self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise EngineUnavailableError("bayesml_amd's regression data passes need an MI355X: there is no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise EngineUnavailableError(f"device {self.device} is not a GPU: there is no CPU fallback")
+        self.device = gpu_device(device, "regression data passes")
         self.stats_len = int(self.lib.regvb_stats_len(self.D))
         self._work = torch.empty(int(self.lib.regvb_stats_work_len(self.D)), dtype=torch.float64, device=self.device)
         self._pwork = self._mu_d = self._linv_d = None
         self.launch_info = ""
-
-    def _stream(self):
-        return _vp(torch.cuda.current_stream(self.device).cuda_stream)
 
     def adopt(self, a):
         return adopt_tensor(a, self.device)
@@ -115,9 +90,9 @@ class RegressionPass:
         y = y.contiguous()
         out = torch.empty(self.stats_len, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.regvb_stats(self.D, _code(x.dtype), x.data_ptr(), x.stride(0) if x.shape[0] > 1 else self.D,
-                                                  _code(y.dtype), y.data_ptr(), x.shape[0], out.data_ptr(), self._work.data_ptr(),
-                                                  self._stream()), "regvb_stats")
+            _check(self.lib.regvb_stats(self.D, _code(x.dtype), x.data_ptr(), x.stride(0) if x.shape[0] > 1 else self.D,
+                                        _code(y.dtype), y.data_ptr(), x.shape[0], out.data_ptr(), self._work.data_ptr(),
+                                        stream_ptr(self.device)), "regvb_stats")
         self.launch_info = "regvb_stats"
         return out
 
@@ -125,8 +100,8 @@ class RegressionPass:
         """The same for the lag windows of a series (degree D - 1)."""
         out = torch.empty(self.stats_len, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.regvb_stats_window(self.D - 1, _code(series.dtype), series.data_ptr(), series.shape[0],
-                                                         int(padding), out.data_ptr(), self._work.data_ptr(), self._stream()),
+            _check(self.lib.regvb_stats_window(self.D - 1, _code(series.dtype), series.data_ptr(), series.shape[0], int(padding),
+                                               out.data_ptr(), self._work.data_ptr(), stream_ptr(self.device)),
                    "regvb_stats_window")
         self.launch_info = "regvb_stats_window"
         return out
@@ -142,9 +117,9 @@ class RegressionPass:
         p_ms = torch.empty(n, dtype=torch.float64, device=self.device)
         p_lambdas = torch.empty(n, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.regvb_predict(self.D, _code(x.dtype), x.data_ptr(), x.stride(0) if n > 1 else self.D, n,
-                                                    mu_d.data_ptr(), linv_d.data_ptr(), float(scale), p_ms.data_ptr(),
-                                                    p_lambdas.data_ptr(), self._pwork.data_ptr(), self._stream()),
+            _check(self.lib.regvb_predict(self.D, _code(x.dtype), x.data_ptr(), x.stride(0) if n > 1 else self.D, n,
+                                          mu_d.data_ptr(), linv_d.data_ptr(), float(scale), p_ms.data_ptr(),
+                                          p_lambdas.data_ptr(), self._pwork.data_ptr(), stream_ptr(self.device)),
                    "regvb_predict")
         self.launch_info = "regvb_predict"
         return p_ms, p_lambdas

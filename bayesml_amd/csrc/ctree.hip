@@ -1,22 +1,14 @@
 // include/ctree.h: argument checks, the layout of the level tables and of the scratch, and the launches of ctree_kernels.h.
 #include "../../include/ctree.h"
 #include "ctree_kernels.h"
+#include "entry.h"
 
 #include <cmath>
-#include <cstdio>
 
 namespace ctree {
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what, hipError_t e = hipSuccess) {
-    if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(g_err, sizeof g_err, "%s", what);
-    return code;
-}
-
-static int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CTREE_OK : fail(CTREE_EHIP, what, e);
-}
+using namespace entry;
+ENTRY_SAME_CODES(CTREE);
+static thread_local Err g_err = {""};
 
 // Sizes of a (k, D) tree; pw[d] = k^d, off[d] = first entry of level d in an all-levels table.
 struct Shape {
@@ -43,16 +35,10 @@ static int shape_of(int k, int D, Shape* sh) {
 }
 
 static int check_shape(const char* who, int k, int D, Shape* sh) {
-    char msg[200];
     const int rc = shape_of(k, D, sh);
-    if (rc == CTREE_EINVAL) {
-        snprintf(msg, sizeof msg, "%s: k and D must be >= 1", who);
-        return fail(rc, msg);
-    }
-    if (rc == CTREE_EUNSUPPORTED) {
-        snprintf(msg, sizeof msg, "%s: k > %d or k^(D+1) > %d is not supported", who, CTREE_MAX_K, CTREE_MAX_SLOTS);
-        return fail(rc, msg);
-    }
+    if (rc == CTREE_EINVAL) return g_err.fail(rc, "%s: k and D must be >= 1", who);
+    if (rc == CTREE_EUNSUPPORTED)
+        return g_err.fail(rc, "%s: k > %d or k^(D+1) > %d is not supported", who, CTREE_MAX_K, CTREE_MAX_SLOTS);
     return CTREE_OK;
 }
 
@@ -63,7 +49,6 @@ static double* level_values(const Shape& sh, void* work) { return (double*)work 
 static int64_t* level_counts(const Shape& sh, void* work) { return (int64_t*)work + count_work(sh) + sh.nodes; }
 
 static int elem_size(int d) { return d == CTREE_U8 ? 1 : d == CTREE_I32 ? 4 : 8; }
-static unsigned grid_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 template <typename T>
 static int launch_count(const void* x_dev, int64_t n, int k, int D, const Shape& sh, void* out_dev, void* work_dev,
@@ -75,18 +60,18 @@ static int launch_count(const void* x_dev, int64_t n, int k, int D, const Shape&
     if (lds_path(sh)) {
         hipLaunchKernelGGL((count_kernel<T, true>), dim3(S), dim3(kThreads), sizeof(unsigned long long) * (size_t)sh.bins, st,
                            (const T*)x_dev, n, span, k, D, sh.bins, (unsigned long long*)nullptr, (int64_t*)work_dev);
-        if (int rc = launched("count_kernel launch")) return rc;
-        hipLaunchKernelGGL(count_combine_kernel, dim3(grid_of(1 + sh.bins)), dim3(kThreads), 0, st, (const int64_t*)work_dev, S,
-                           1 + sh.bins, n, out);
-        return launched("count_combine_kernel launch");
+        if (int rc = g_err.launched("count_kernel launch")) return rc;
+        hipLaunchKernelGGL(count_combine_kernel, dim3(grid_of(1 + sh.bins, kThreads)), dim3(kThreads), 0, st,
+                           (const int64_t*)work_dev, S, 1 + sh.bins, n, out);
+        return g_err.launched("count_combine_kernel launch");
     }
     const hipError_t e = hipMemsetAsync(out + 2, 0, sizeof(int64_t) * (size_t)sh.bins, st);
-    if (e != hipSuccess) return fail(CTREE_EHIP, "ctree_count: hipMemsetAsync", e);
+    if (e != hipSuccess) return g_err.hip(CTREE_EHIP, "ctree_count: hipMemsetAsync", e);
     hipLaunchKernelGGL((count_kernel<T, false>), dim3(S), dim3(kThreads), 0, st, (const T*)x_dev, n, span, k, D, sh.bins,
                        (unsigned long long*)(out + 2), (int64_t*)work_dev);
-    if (int rc = launched("count_kernel launch")) return rc;
+    if (int rc = g_err.launched("count_kernel launch")) return rc;
     hipLaunchKernelGGL(count_combine_kernel, dim3(1), dim3(kThreads), 0, st, (const int64_t*)work_dev, S, (int64_t)1, n, out);
-    return launched("count_combine_kernel launch");
+    return g_err.launched("count_combine_kernel launch");
 }
 
 // hn_g^((k^(D-depth) - 1)/(k - 1) - 1), the reference's price of a full subtree under a missing child of a node at `depth`
@@ -102,7 +87,7 @@ using namespace ctree;
 extern "C" {
 
 int ctree_abi_version(void) { return CTREE_ABI_VERSION; }
-const char* ctree_last_error(void) { return g_err; }
+const char* ctree_last_error(void) { return g_err.msg; }
 
 int64_t ctree_table_len(int k, int D, int level) {
     Shape sh;
@@ -119,13 +104,14 @@ int64_t ctree_work_len(int k, int D) {
 int ctree_count(int dtype, const void* x_dev, int64_t n, int k, int D, void* out_dev, void* work_dev, void* stream) {
     Shape sh;
     if (int rc = check_shape("ctree_count", k, D, &sh)) return rc;
-    if (dtype < CTREE_U8 || dtype > CTREE_I64) return fail(CTREE_EINVAL, "ctree_count: dtype must be CTREE_U8, CTREE_I32 or CTREE_I64");
-    if (n < 1) return fail(CTREE_EINVAL, "ctree_count: n must be >= 1");
-    if (!x_dev || !out_dev || !work_dev) return fail(CTREE_EINVAL, "ctree_count: null pointer");
-    if ((uintptr_t)x_dev % (uintptr_t)elem_size(dtype) != 0)
-        return fail(CTREE_EINVAL, "ctree_count: x_dev must be aligned to its element size");
-    if ((uintptr_t)out_dev % 8 != 0 || (uintptr_t)work_dev % 8 != 0)
-        return fail(CTREE_EINVAL, "ctree_count: out_dev and work_dev must be aligned to 8 bytes");
+    if (dtype < CTREE_U8 || dtype > CTREE_I64)
+        return g_err.fail(CTREE_EINVAL, "ctree_count: dtype must be CTREE_U8, CTREE_I32 or CTREE_I64");
+    if (n < 1) return g_err.fail(CTREE_EINVAL, "ctree_count: n must be >= 1");
+    if (!x_dev || !out_dev || !work_dev) return g_err.fail(CTREE_EINVAL, "ctree_count: null pointer");
+    if (misaligned(x_dev, elem_size(dtype)))
+        return g_err.fail(CTREE_EINVAL, "ctree_count: x_dev must be aligned to its element size");
+    if (any_misaligned(8, out_dev, work_dev))
+        return g_err.fail(CTREE_EINVAL, "ctree_count: out_dev and work_dev must be aligned to 8 bytes");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == CTREE_U8) return launch_count<uint8_t>(x_dev, n, k, D, sh, out_dev, work_dev, st);
     if (dtype == CTREE_I32) return launch_count<int32_t>(x_dev, n, k, D, sh, out_dev, work_dev, st);
@@ -136,14 +122,12 @@ int ctree_sweep(int k, int D, const void* cnt_dev, const void* head_dev, int n_h
                 void* exists_dev, double hn_g, const void* hn_beta_dev, void* cnt_levels_dev, void* work_dev, void* stream) {
     Shape sh;
     if (int rc = check_shape("ctree_sweep", k, D, &sh)) return rc;
-    if (n_head < 0 || n_head > D) return fail(CTREE_EINVAL, "ctree_sweep: n_head must be in 0..D");
+    if (n_head < 0 || n_head > D) return g_err.fail(CTREE_EINVAL, "ctree_sweep: n_head must be in 0..D");
     if (!cnt_dev || !beta_dev || !g_dev || !exists_dev || !hn_beta_dev || !work_dev || (n_head > 0 && !head_dev))
-        return fail(CTREE_EINVAL, "ctree_sweep: null pointer");
-    if (!(hn_g >= 0.0 && hn_g <= 1.0)) return fail(CTREE_EINVAL, "ctree_sweep: hn_g must be in [0, 1]");
-    if ((uintptr_t)cnt_dev % 8 != 0 || (uintptr_t)beta_dev % 8 != 0 || (uintptr_t)g_dev % 8 != 0 ||
-        (uintptr_t)hn_beta_dev % 8 != 0 || (uintptr_t)cnt_levels_dev % 8 != 0 || (uintptr_t)work_dev % 8 != 0 ||
-        (uintptr_t)head_dev % 4 != 0)
-        return fail(CTREE_EINVAL, "ctree_sweep: misaligned pointer");
+        return g_err.fail(CTREE_EINVAL, "ctree_sweep: null pointer");
+    if (!(hn_g >= 0.0 && hn_g <= 1.0)) return g_err.fail(CTREE_EINVAL, "ctree_sweep: hn_g must be in [0, 1]");
+    if (any_misaligned(8, cnt_dev, beta_dev, g_dev, hn_beta_dev, cnt_levels_dev, work_dev) || misaligned(head_dev, 4))
+        return g_err.fail(CTREE_EINVAL, "ctree_sweep: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     double* lnw = level_values(sh, work_dev);
     int64_t* cl = cnt_levels_dev ? (int64_t*)cnt_levels_dev : level_counts(sh, work_dev);
@@ -151,15 +135,15 @@ int ctree_sweep(int k, int D, const void* cnt_dev, const void* head_dev, int n_h
     double* g = (double*)g_dev;
     uint8_t* ex = (uint8_t*)exists_dev;
     const double* hb = (const double*)hn_beta_dev;
-    hipLaunchKernelGGL(sweep_deepest_kernel, dim3(grid_of(sh.pw[D])), dim3(kThreads), 0, st, k, sh.pw[D], (const int64_t*)cnt_dev,
-                       beta + sh.off[D] * k, g + sh.off[D], ex + sh.off[D], hb, lnw + sh.off[D]);
-    if (int rc = launched("sweep_deepest_kernel launch")) return rc;
+    hipLaunchKernelGGL(sweep_deepest_kernel, dim3(grid_of(sh.pw[D], kThreads)), dim3(kThreads), 0, st, k, sh.pw[D],
+                       (const int64_t*)cnt_dev, beta + sh.off[D] * k, g + sh.off[D], ex + sh.off[D], hb, lnw + sh.off[D]);
+    if (int rc = g_err.launched("sweep_deepest_kernel launch")) return rc;
     for (int d = D - 1; d >= 0; --d) {
         const int64_t* child = d + 1 == D ? (const int64_t*)cnt_dev : cl + sh.off[d + 1] * k;
-        hipLaunchKernelGGL(sweep_level_kernel, dim3(grid_of(sh.pw[d])), dim3(kThreads), 0, st, k, d, sh.pw[d], child,
+        hipLaunchKernelGGL(sweep_level_kernel, dim3(grid_of(sh.pw[d], kThreads)), dim3(kThreads), 0, st, k, d, sh.pw[d], child,
                            cl + sh.off[d] * k, (const double*)(lnw + sh.off[d + 1]), lnw + sh.off[d], beta + sh.off[d] * k,
                            g + sh.off[d], ex + sh.off[d], hn_g, hb, (const int32_t*)head_dev, n_head);
-        if (int rc = launched("sweep_level_kernel launch")) return rc;
+        if (int rc = g_err.launched("sweep_level_kernel launch")) return rc;
     }
     return CTREE_OK;
 }
@@ -168,9 +152,9 @@ int ctree_map(int k, int D, const void* g_dev, const void* exists_dev, double hn
               void* stream) {
     Shape sh;
     if (int rc = check_shape("ctree_map", k, D, &sh)) return rc;
-    if (!g_dev || !exists_dev || !map_leaf_dev || !work_dev) return fail(CTREE_EINVAL, "ctree_map: null pointer");
-    if (!(hn_g >= 0.0 && hn_g <= 1.0)) return fail(CTREE_EINVAL, "ctree_map: hn_g must be in [0, 1]");
-    if ((uintptr_t)g_dev % 8 != 0 || (uintptr_t)work_dev % 8 != 0) return fail(CTREE_EINVAL, "ctree_map: misaligned pointer");
+    if (!g_dev || !exists_dev || !map_leaf_dev || !work_dev) return g_err.fail(CTREE_EINVAL, "ctree_map: null pointer");
+    if (!(hn_g >= 0.0 && hn_g <= 1.0)) return g_err.fail(CTREE_EINVAL, "ctree_map: hn_g must be in [0, 1]");
+    if (any_misaligned(8, g_dev, work_dev)) return g_err.fail(CTREE_EINVAL, "ctree_map: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     double* val = level_values(sh, work_dev);
     const double* g = (const double*)g_dev;
@@ -181,10 +165,10 @@ int ctree_map(int k, int D, const void* g_dev, const void* exists_dev, double hn
         const double pw_parent = d > 0 ? subtree_pow(hn_g, k, D, d - 1, sh) : 1.0;
         // (the neighbouring levels' pointers are not read at d = D and d = 0; they point at this level's tables there)
         const int dc = d < D ? d + 1 : d, dp = d > 0 ? d - 1 : d;
-        hipLaunchKernelGGL(map_level_kernel, dim3(grid_of(sh.pw[d])), dim3(kThreads), 0, st, k, d, D, sh.pw[d], g + sh.off[d],
-                           ex + sh.off[d], ex + sh.off[dc], (const double*)(val + sh.off[dc]), g + sh.off[dp], ex + sh.off[dp],
-                           pw_here, pw_parent, val + sh.off[d], ml + sh.off[d]);
-        if (int rc = launched("map_level_kernel launch")) return rc;
+        hipLaunchKernelGGL(map_level_kernel, dim3(grid_of(sh.pw[d], kThreads)), dim3(kThreads), 0, st, k, d, D, sh.pw[d],
+                           g + sh.off[d], ex + sh.off[d], ex + sh.off[dc], (const double*)(val + sh.off[dc]), g + sh.off[dp],
+                           ex + sh.off[dp], pw_here, pw_parent, val + sh.off[d], ml + sh.off[d]);
+        if (int rc = g_err.launched("map_level_kernel launch")) return rc;
     }
     return CTREE_OK;
 }

@@ -1,16 +1,12 @@
 // include/expfam.h: argument checks, the split of a sample into workgroup ranges, and the launches of expfam_kernels.h.
 #include "../../include/expfam.h"
+#include "entry.h"
 #include "expfam_kernels.h"
 
-#include <cstdio>
-
 namespace expfam {
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what, hipError_t e = hipSuccess) {
-    if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(g_err, sizeof g_err, "%s", what);
-    return code;
-}
+using namespace entry;
+ENTRY_SAME_CODES(EXPFAM);
+static thread_local Err g_err = {""};
 
 static bool is_int_dtype(int d) { return d == EXPFAM_U8 || d == EXPFAM_I32 || d == EXPFAM_I64; }
 static bool is_float_dtype(int d) { return d == EXPFAM_F32 || d == EXPFAM_F64; }
@@ -31,47 +27,21 @@ static int slab_len(int family, int degree) {
 
 // The checks every entry point shares; `ints` says which dtypes the family reads.
 static int check_common(const char* who, bool ints, int dtype, const void* x, int64_t n, const void* stats, const void* work) {
-    char msg[160];
-    if (dtype < EXPFAM_U8 || dtype > EXPFAM_F64) {
-        snprintf(msg, sizeof msg, "%s: dtype must be an expfam_dtype", who);
-        return fail(EXPFAM_EINVAL, msg);
-    }
-    if (ints ? !is_int_dtype(dtype) : !is_float_dtype(dtype)) {
-        snprintf(msg, sizeof msg, "%s: dtype must be %s", who,
-                 ints ? "EXPFAM_U8, EXPFAM_I32 or EXPFAM_I64" : "EXPFAM_F32 or EXPFAM_F64");
-        return fail(EXPFAM_EINVAL, msg);
-    }
-    if (n < 1) {
-        snprintf(msg, sizeof msg, "%s: n must be >= 1", who);
-        return fail(EXPFAM_EINVAL, msg);
-    }
-    if (!x || !stats || !work) {
-        snprintf(msg, sizeof msg, "%s: null pointer", who);
-        return fail(EXPFAM_EINVAL, msg);
-    }
-    if ((uintptr_t)x % (uintptr_t)elem_size(dtype) != 0) {
-        snprintf(msg, sizeof msg, "%s: x_dev must be aligned to its element size", who);
-        return fail(EXPFAM_EINVAL, msg);
-    }
+    if (dtype < EXPFAM_U8 || dtype > EXPFAM_F64) return g_err.fail(EXPFAM_EINVAL, "%s: dtype must be an expfam_dtype", who);
+    if (ints ? !is_int_dtype(dtype) : !is_float_dtype(dtype))
+        return g_err.fail(EXPFAM_EINVAL, "%s: dtype must be %s", who,
+                          ints ? "EXPFAM_U8, EXPFAM_I32 or EXPFAM_I64" : "EXPFAM_F32 or EXPFAM_F64");
+    if (n < 1) return g_err.fail(EXPFAM_EINVAL, "%s: n must be >= 1", who);
+    if (!x || !stats || !work) return g_err.fail(EXPFAM_EINVAL, "%s: null pointer", who);
+    if (misaligned(x, elem_size(dtype))) return g_err.fail(EXPFAM_EINVAL, "%s: x_dev must be aligned to its element size", who);
     return EXPFAM_OK;
 }
 
 static int check_degree(const char* who, int degree) {
-    char msg[160];
-    if (degree < 1) {
-        snprintf(msg, sizeof msg, "%s: degree must be >= 1", who);
-        return fail(EXPFAM_EINVAL, msg);
-    }
-    if (degree > EXPFAM_MAX_DEGREE) {
-        snprintf(msg, sizeof msg, "%s: degree > %d is not supported", who, EXPFAM_MAX_DEGREE);
-        return fail(EXPFAM_EUNSUPPORTED, msg);
-    }
+    if (degree < 1) return g_err.fail(EXPFAM_EINVAL, "%s: degree must be >= 1", who);
+    if (degree > EXPFAM_MAX_DEGREE)
+        return g_err.fail(EXPFAM_EUNSUPPORTED, "%s: degree > %d is not supported", who, EXPFAM_MAX_DEGREE);
     return EXPFAM_OK;
-}
-
-static int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? EXPFAM_OK : fail(EXPFAM_EHIP, what, e);
 }
 
 // Ranges of whole 16-byte vectors, the same for the same pointer alignment and n (run-to-run identical sums).
@@ -89,14 +59,14 @@ static int launch_stream(const void* x_dev, int64_t n, int degree, int max_slot,
     const int len = ACC::slab_len(degree);
     hipLaunchKernelGGL((stream_kernel<T, ACC>), dim3(S), dim3(kThreads), ACC::lds_bytes(degree), st, x, n, head, nvec, vps,
                        degree, (int64_t*)work_dev);
-    if (int rc = launched("stream_kernel launch")) return rc;
+    if (int rc = g_err.launched("stream_kernel launch")) return rc;
     if (normal) {
         hipLaunchKernelGGL(combine_normal_kernel, dim3(1), dim3(64), 0, st, (const int64_t*)work_dev, S, n, (int64_t*)stats_dev);
-        return launched("combine_normal_kernel launch");
+        return g_err.launched("combine_normal_kernel launch");
     }
-    hipLaunchKernelGGL(combine_kernel, dim3((len + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (const int64_t*)work_dev,
+    hipLaunchKernelGGL(combine_kernel, dim3(grid_of(len, kThreads)), dim3(kThreads), 0, st, (const int64_t*)work_dev,
                        S, len, n, max_slot, dsum_slot, (int64_t*)stats_dev);
-    return launched("combine_kernel launch");
+    return g_err.launched("combine_kernel launch");
 }
 
 template <template <typename> class ACC>
@@ -127,11 +97,11 @@ static int launch_onehot(const void* x_dev, int64_t n, int degree, int64_t ld, v
     const int S = (int)((n + rps - 1) / rps);
     hipLaunchKernelGGL((onehot_kernel<T>), dim3(S), dim3(kThreads), sizeof(unsigned long long) * (size_t)degree, st,
                        (const T*)x_dev, n, degree, ld, W, rps, (int64_t*)work_dev);
-    if (int rc = launched("onehot_kernel launch")) return rc;
+    if (int rc = g_err.launched("onehot_kernel launch")) return rc;
     const int len = 1 + degree;
-    hipLaunchKernelGGL(combine_kernel, dim3((len + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (const int64_t*)work_dev,
+    hipLaunchKernelGGL(combine_kernel, dim3(grid_of(len, kThreads)), dim3(kThreads), 0, st, (const int64_t*)work_dev,
                        S, len, n, -1, -1, (int64_t*)stats_dev);
-    return launched("combine_kernel launch");
+    return g_err.launched("combine_kernel launch");
 }
 }  // namespace expfam
 
@@ -140,7 +110,7 @@ using namespace expfam;
 extern "C" {
 
 int expfam_abi_version(void) { return EXPFAM_ABI_VERSION; }
-const char* expfam_last_error(void) { return g_err; }
+const char* expfam_last_error(void) { return g_err.msg; }
 
 int64_t expfam_stats_len(int family, int degree) {
     if (family < EXPFAM_BERNOULLI || family > EXPFAM_NORMAL) return -1;
@@ -172,7 +142,7 @@ int expfam_stats_onehot(int dtype, const void* x_dev, int64_t n, int degree, int
                         void* stream) {
     if (int rc = check_degree("expfam_stats_onehot", degree)) return rc;
     if (int rc = check_common("expfam_stats_onehot", true, dtype, x_dev, n, stats_dev, work_dev)) return rc;
-    if (ld < degree) return fail(EXPFAM_EINVAL, "expfam_stats_onehot: ld must be >= degree");
+    if (ld < degree) return g_err.fail(EXPFAM_EINVAL, "expfam_stats_onehot: ld must be >= degree");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == EXPFAM_U8) return launch_onehot<uint8_t>(x_dev, n, degree, ld, stats_dev, work_dev, st);
     if (dtype == EXPFAM_I32) return launch_onehot<int32_t>(x_dev, n, degree, ld, stats_dev, work_dev, st);

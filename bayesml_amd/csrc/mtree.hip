@@ -1,21 +1,12 @@
 // include/mtree.h: argument checks, the layout of the scratch, and the launches of mtree_kernels.h.
 #include "../../include/mtree.h"
+#include "entry.h"
 #include "mtree_kernels.h"
 
-#include <cstdio>
-
 namespace mtree {
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what, hipError_t e = hipSuccess) {
-    if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(g_err, sizeof g_err, "%s", what);
-    return code;
-}
-
-static int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MTREE_OK : fail(MTREE_EHIP, what, e);
-}
+using namespace entry;
+ENTRY_SAME_CODES(MTREE);
+static thread_local Err g_err = {""};
 
 // rows of one call: what grid_of() can hold in a grid's x dimension
 constexpr int64_t kMaxRows = (int64_t)0x7fffffff * kThreads;
@@ -41,70 +32,47 @@ static int cols_of(int family, int degree, Cols* c) {
 }
 
 static int check_family(const char* who, int family, int degree, Cols* c) {
-    char msg[200];
     const int rc = cols_of(family, degree, c);
-    if (rc == MTREE_EINVAL) {
-        snprintf(msg, sizeof msg, "%s: unknown family, or degree < 1", who);
-        return fail(rc, msg);
-    }
-    if (rc == MTREE_EUNSUPPORTED) {
-        snprintf(msg, sizeof msg, "%s: a categorical degree above %d is not supported", who, MTREE_MAX_DEGREE);
-        return fail(rc, msg);
-    }
+    if (rc == MTREE_EINVAL) return g_err.fail(rc, "%s: unknown family, or degree < 1", who);
+    if (rc == MTREE_EUNSUPPORTED)
+        return g_err.fail(rc, "%s: a categorical degree above %d is not supported", who, MTREE_MAX_DEGREE);
     return MTREE_OK;
 }
 
 static int check_forest(const char* who, const mtree_forest* f, Forest* out) {
-    char msg[240];
-    if (!f) {
-        snprintf(msg, sizeof msg, "%s: null forest", who);
-        return fail(MTREE_EINVAL, msg);
-    }
+    if (!f) return g_err.fail(MTREE_EINVAL, "%s: null forest", who);
     if (f->n_trees < 1 || f->n_nodes < f->n_trees || f->n_thr < 0 || f->max_tree_nodes < 1 || f->max_children < 0 ||
         f->max_depth < 0 || f->dim_cont < 0 || f->dim_cat < 0 || f->dim_cont + f->dim_cat < 1 ||
-        f->max_tree_nodes > f->n_nodes) {
-        snprintf(msg, sizeof msg, "%s: inconsistent forest sizes", who);
-        return fail(MTREE_EINVAL, msg);
-    }
+        f->max_tree_nodes > f->n_nodes)
+        return g_err.fail(MTREE_EINVAL, "%s: inconsistent forest sizes", who);
     if (f->n_trees > MTREE_MAX_TREES || f->max_tree_nodes > MTREE_MAX_NODES || f->max_children > MTREE_MAX_CHILDREN ||
-        f->max_depth > MTREE_MAX_DEPTH) {
-        snprintf(msg, sizeof msg, "%s: more than %d trees, %d nodes per tree, %d children per node or depth %d is not supported",
-                 who, MTREE_MAX_TREES, MTREE_MAX_NODES, MTREE_MAX_CHILDREN, MTREE_MAX_DEPTH);
-        return fail(MTREE_EUNSUPPORTED, msg);
-    }
+        f->max_depth > MTREE_MAX_DEPTH)
+        return g_err.fail(MTREE_EUNSUPPORTED,
+                          "%s: more than %d trees, %d nodes per tree, %d children per node or depth %d is not supported", who,
+                          MTREE_MAX_TREES, MTREE_MAX_NODES, MTREE_MAX_CHILDREN, MTREE_MAX_DEPTH);
     if (!f->tree_off_dev || !f->feat_dev || !f->child0_dev || !f->nchild_dev || !f->thr_off_dev || !f->depth_dev ||
-        (f->n_thr > 0 && !f->thr_dev)) {
-        snprintf(msg, sizeof msg, "%s: null forest table", who);
-        return fail(MTREE_EINVAL, msg);
-    }
-    if ((uintptr_t)f->tree_off_dev % 4 || (uintptr_t)f->feat_dev % 4 || (uintptr_t)f->child0_dev % 4 ||
-        (uintptr_t)f->nchild_dev % 4 || (uintptr_t)f->thr_off_dev % 4 || (uintptr_t)f->depth_dev % 4 ||
-        (uintptr_t)f->thr_dev % 8) {
-        snprintf(msg, sizeof msg, "%s: misaligned forest table", who);
-        return fail(MTREE_EINVAL, msg);
-    }
+        (f->n_thr > 0 && !f->thr_dev))
+        return g_err.fail(MTREE_EINVAL, "%s: null forest table", who);
+    if (any_misaligned(4, f->tree_off_dev, f->feat_dev, f->child0_dev, f->nchild_dev, f->thr_off_dev, f->depth_dev) ||
+        misaligned(f->thr_dev, 8))
+        return g_err.fail(MTREE_EINVAL, "%s: misaligned forest table", who);
     *out = {f->n_trees, f->n_nodes, f->n_thr, f->max_depth, f->dim_cont, f->dim_cat, f->tree_off_dev, f->feat_dev,
             f->child0_dev, f->nchild_dev, f->thr_off_dev, f->depth_dev, f->thr_dev};
     return MTREE_OK;
 }
 
 static int check_x(const char* who, const Forest& f, int xc_dtype, const void* xc, int xk_dtype, const void* xk, int64_t n) {
-    char msg[200];
     const char* bad = nullptr;
     if (n < 1) bad = "n must be >= 1";
     else if (n > kMaxRows) bad = "n is too large (more than 2^31 - 1 workgroups of rows)";
     else if (f.dim_cont > 0 && xc_dtype != MTREE_F32 && xc_dtype != MTREE_F64) bad = "xc_dtype must be MTREE_F32 or MTREE_F64";
     else if (f.dim_cat > 0 && (xk_dtype < MTREE_U8 || xk_dtype > MTREE_I64)) bad = "xk_dtype must be MTREE_U8, MTREE_I32 or MTREE_I64";
     else if ((f.dim_cont > 0 && !xc) || (f.dim_cat > 0 && !xk)) bad = "null sample pointer";
-    else if (f.dim_cont > 0 && (uintptr_t)xc % (xc_dtype == MTREE_F32 ? 4 : 8)) bad = "xc_dev must be aligned to its element size";
-    else if (f.dim_cat > 0 && (uintptr_t)xk % (xk_dtype == MTREE_U8 ? 1 : xk_dtype == MTREE_I32 ? 4 : 8))
+    else if (f.dim_cont > 0 && misaligned(xc, xc_dtype == MTREE_F32 ? 4 : 8)) bad = "xc_dev must be aligned to its element size";
+    else if (f.dim_cat > 0 && misaligned(xk, xk_dtype == MTREE_U8 ? 1 : xk_dtype == MTREE_I32 ? 4 : 8))
         bad = "xk_dev must be aligned to its element size";
-    if (!bad) return MTREE_OK;
-    snprintf(msg, sizeof msg, "%s: %s", who, bad);
-    return fail(MTREE_EINVAL, msg);
+    return bad ? g_err.fail(MTREE_EINVAL, "%s: %s", who, bad) : MTREE_OK;
 }
-
-static unsigned grid_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // The six (continuous, categorical) element types.  A dimension of 0 takes the first type of its kind; it is never read.
 #define MTREE_DISPATCH(xc_dtype, xk_dtype, CALL)                                   \
@@ -127,7 +95,7 @@ using namespace mtree;
 extern "C" {
 
 int mtree_abi_version(void) { return MTREE_ABI_VERSION; }
-const char* mtree_last_error(void) { return g_err; }
+const char* mtree_last_error(void) { return g_err.msg; }
 
 int mtree_stat_cols(int family, int degree, int* n_int, int* n_real, int* n_post) {
     Cols c;
@@ -150,35 +118,34 @@ int mtree_route(const mtree_forest* f, int xc_dtype, const void* xc_dev, int xk_
     Forest F;
     if (int rc = check_forest("mtree_route", f, &F)) return rc;
     if (int rc = check_x("mtree_route", F, xc_dtype, xc_dev, xk_dtype, xk_dev, n)) return rc;
-    if (!stop_dev || !bad_dev || (F.dim_cat > 0 && !cat_card_dev)) return fail(MTREE_EINVAL, "mtree_route: null pointer");
-    if ((uintptr_t)stop_dev % 4 || (uintptr_t)path_dev % 4 || (uintptr_t)cat_card_dev % 4 || (uintptr_t)bad_dev % 8)
-        return fail(MTREE_EINVAL, "mtree_route: misaligned pointer");
+    if (!stop_dev || !bad_dev || (F.dim_cat > 0 && !cat_card_dev)) return g_err.fail(MTREE_EINVAL, "mtree_route: null pointer");
+    if (any_misaligned(4, stop_dev, path_dev, cat_card_dev) || misaligned(bad_dev, 8))
+        return g_err.fail(MTREE_EINVAL, "mtree_route: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int64_t), st);
-    if (e != hipSuccess) return fail(MTREE_EHIP, "mtree_route: hipMemsetAsync", e);
-    const dim3 grid(grid_of(n), (unsigned)F.n_trees);
+    if (e != hipSuccess) return g_err.hip(MTREE_EHIP, "mtree_route: hipMemsetAsync", e);
+    const dim3 grid(grid_of(n, kThreads), (unsigned)F.n_trees);
 #define MTREE_ROUTE(TC, TK)                                                                                              \
     hipLaunchKernelGGL((route_kernel<TC, TK>), grid, dim3(kThreads), 0, st, F, (const TC*)xc_dev, (const TK*)xk_dev, \
                        cat_card_dev, n, stop_dev, path_dev, (unsigned long long*)bad_dev)
     MTREE_DISPATCH(xc_dtype, xk_dtype, MTREE_ROUTE);
 #undef MTREE_ROUTE
-    return launched("route_kernel launch");
+    return g_err.launched("route_kernel launch");
 }
 
-int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev,
-                 const double* pivot_dev, int64_t n, int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev,
-                 void* stream) {
+int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev, int64_t n,
+                 int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev, void* stream) {
     Forest F;
     Cols c;
     if (int rc = check_forest("mtree_reduce", f, &F)) return rc;
     if (int rc = check_family("mtree_reduce", family, degree, &c)) return rc;
-    if (n < 1 || n > kMaxRows) return fail(MTREE_EINVAL, "mtree_reduce: n must be >= 1 (and at most (2^31 - 1) * 256)");
-    if (n_slabs < 1 || n_slabs > MTREE_MAX_SLABS) return fail(MTREE_EINVAL, "mtree_reduce: n_slabs must be in 1..MTREE_MAX_SLABS");
+    if (n < 1 || n > kMaxRows) return g_err.fail(MTREE_EINVAL, "mtree_reduce: n must be >= 1 (and at most (2^31 - 1) * 256)");
+    if (n_slabs < 1 || n_slabs > MTREE_MAX_SLABS)
+        return g_err.fail(MTREE_EINVAL, "mtree_reduce: n_slabs must be in 1..MTREE_MAX_SLABS");
     if (!stop_dev || !y_dev || !stat_int_dev || !work_dev || (c.nr > 0 && !stat_real_dev))
-        return fail(MTREE_EINVAL, "mtree_reduce: null pointer");
-    if ((uintptr_t)stop_dev % 4 || (uintptr_t)y_dev % 8 || (uintptr_t)pivot_dev % 8 || (uintptr_t)stat_int_dev % 8 ||
-        (uintptr_t)stat_real_dev % 8 || (uintptr_t)work_dev % 8)
-        return fail(MTREE_EINVAL, "mtree_reduce: misaligned pointer");
+        return g_err.fail(MTREE_EINVAL, "mtree_reduce: null pointer");
+    if (misaligned(stop_dev, 4) || any_misaligned(8, y_dev, stat_int_dev, stat_real_dev, work_dev))
+        return g_err.fail(MTREE_EINVAL, "mtree_reduce: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     const int S = n_slabs, nr1 = c.nr > 1 ? 1 : c.nr;
     unsigned long long* wi = (unsigned long long*)work_dev + F.n_nodes;
@@ -190,18 +157,18 @@ int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* s
                            F, family, degree, c.ni, nr1, stop_dev, y_dev, (const double*)nullptr, n, S, wi, wr);
     } else {
         const hipError_t e = hipMemsetAsync(wi, 0, sizeof(double) * (size_t)S * F.n_nodes * (c.ni + nr1), st);
-        if (e != hipSuccess) return fail(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
+        if (e != hipSuccess) return g_err.hip(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
         hipLaunchKernelGGL((reduce_kernel<false>), grid, dim3(kWave), 0, st, F, family, degree, c.ni, nr1, stop_dev, y_dev,
                            (const double*)nullptr, n, S, wi, wr);
     }
-    if (int rc = launched("reduce_kernel launch")) return rc;
-    hipLaunchKernelGGL((combine_kernel<int64_t>), dim3(grid_of((int64_t)F.n_nodes * c.ni)), dim3(kThreads), 0, st,
+    if (int rc = g_err.launched("reduce_kernel launch")) return rc;
+    hipLaunchKernelGGL((combine_kernel<int64_t>), dim3(grid_of((int64_t)F.n_nodes * c.ni, kThreads)), dim3(kThreads), 0, st,
                        (const int64_t*)wi, S, (int64_t)F.n_nodes, c.ni, c.ni, 0, stat_int_dev);
-    if (int rc = launched("combine_kernel launch")) return rc;
+    if (int rc = g_err.launched("combine_kernel launch")) return rc;
     if (nr1 > 0) {
-        hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of(F.n_nodes)), dim3(kThreads), 0, st, (const double*)wr, S,
-                           (int64_t)F.n_nodes, 1, c.nr, 0, stat_real_dev);
-        if (int rc = launched("combine_kernel launch")) return rc;
+        hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of(F.n_nodes, kThreads)), dim3(kThreads), 0, st,
+                           (const double*)wr, S, (int64_t)F.n_nodes, 1, c.nr, 0, stat_real_dev);
+        if (int rc = g_err.launched("combine_kernel launch")) return rc;
     }
     if (family != MTREE_NORMAL) return MTREE_OK;
     // The second pass: two columns per node, in the scratch of the first pass (ni + 1 = 2 columns, combined already).
@@ -213,33 +180,32 @@ int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* s
                            w2);
     } else {
         const hipError_t e = hipMemsetAsync(w2, 0, sizeof(double) * (size_t)S * F.n_nodes * 2, st);
-        if (e != hipSuccess) return fail(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
+        if (e != hipSuccess) return g_err.hip(MTREE_EHIP, "mtree_reduce: hipMemsetAsync", e);
         hipLaunchKernelGGL((reduce_centred_kernel<false>), grid, dim3(kWave), 0, st, F, stop_dev, (const double*)y_dev, n, S,
                            (const int64_t*)stat_int_dev, (const double*)stat_real_dev, c.nr, w2);
     }
-    if (int rc = launched("reduce_centred_kernel launch")) return rc;
-    hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of((int64_t)F.n_nodes * 2)), dim3(kThreads), 0, st, (const double*)w2,
-                       S, (int64_t)F.n_nodes, 2, c.nr, 1, stat_real_dev);
-    return launched("combine_kernel launch");
+    if (int rc = g_err.launched("reduce_centred_kernel launch")) return rc;
+    hipLaunchKernelGGL((combine_kernel<double>), dim3(grid_of((int64_t)F.n_nodes * 2, kThreads)), dim3(kThreads), 0, st,
+                       (const double*)w2, S, (int64_t)F.n_nodes, 2, c.nr, 1, stat_real_dev);
+    return g_err.launched("combine_kernel launch");
 }
 
 int mtree_sweep(const mtree_forest* f, int family, int degree, int64_t* stat_int_dev, double* stat_real_dev,
-                const double* pivot_dev, const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev,
-                double* lcm_dev, double* lnp_dev, void* work_dev, void* stream) {
+                const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev, double* lcm_dev, double* lnp_dev,
+                void* work_dev, void* stream) {
     Forest F;
     Cols c;
     if (int rc = check_forest("mtree_sweep", f, &F)) return rc;
     if (int rc = check_family("mtree_sweep", family, degree, &c)) return rc;
-    if (!stat_int_dev || (c.nr > 0 && !stat_real_dev) || !h0_dev || !post_dev || !g_dev || !lml_dev || !lcm_dev || !lnp_dev || !work_dev)
-        return fail(MTREE_EINVAL, "mtree_sweep: null pointer");
-    if ((uintptr_t)stat_int_dev % 8 || (uintptr_t)stat_real_dev % 8 || (uintptr_t)pivot_dev % 8 || (uintptr_t)h0_dev % 8 ||
-        (uintptr_t)post_dev % 8 || (uintptr_t)g_dev % 8 || (uintptr_t)lml_dev % 8 || (uintptr_t)lcm_dev % 8 || (uintptr_t)lnp_dev % 8 ||
-        (uintptr_t)work_dev % 8)
-        return fail(MTREE_EINVAL, "mtree_sweep: misaligned pointer");
+    if (!stat_int_dev || (c.nr > 0 && !stat_real_dev) || !h0_dev || !post_dev || !g_dev || !lml_dev || !lcm_dev || !lnp_dev ||
+        !work_dev)
+        return g_err.fail(MTREE_EINVAL, "mtree_sweep: null pointer");
+    if (any_misaligned(8, stat_int_dev, stat_real_dev, h0_dev, post_dev, g_dev, lml_dev, lcm_dev, lnp_dev, work_dev))
+        return g_err.fail(MTREE_EINVAL, "mtree_sweep: misaligned pointer");
     hipLaunchKernelGGL(sweep_kernel, dim3((unsigned)F.n_trees), dim3(kThreads), 0, (hipStream_t)stream, F, family, degree, c.ni,
                        c.nr, c.np, stat_int_dev, stat_real_dev, h0_dev, post_dev, g_dev, lml_dev, lcm_dev, lnp_dev,
                        (double*)work_dev);
-    return launched("sweep_kernel launch");
+    return g_err.launched("sweep_kernel launch");
 }
 
 int mtree_predict(const mtree_forest* f, int family, int degree, int mode, int xc_dtype, const void* xc_dev, int xk_dtype,
@@ -249,27 +215,26 @@ int mtree_predict(const mtree_forest* f, int family, int degree, int mode, int x
     Cols c;
     if (int rc = check_forest("mtree_predict", f, &F)) return rc;
     if (int rc = check_family("mtree_predict", family, degree, &c)) return rc;
-    if (mode < MTREE_PRED_MEAN || mode > MTREE_PRED_VAR) return fail(MTREE_EINVAL, "mtree_predict: unknown mode");
+    if (mode < MTREE_PRED_MEAN || mode > MTREE_PRED_VAR) return g_err.fail(MTREE_EINVAL, "mtree_predict: unknown mode");
     const bool clf = family == MTREE_BERNOULLI || family == MTREE_CATEGORICAL;
     if ((mode == MTREE_PRED_MEAN && clf) || ((mode == MTREE_PRED_PROBA || mode == MTREE_PRED_CLASS) && !clf) ||
         (mode == MTREE_PRED_VAR && family != MTREE_NORMAL))
-        return fail(MTREE_EINVAL, "mtree_predict: the family has no such read-out");
+        return g_err.fail(MTREE_EINVAL, "mtree_predict: the family has no such read-out");
     if (int rc = check_x("mtree_predict", F, xc_dtype, xc_dev, xk_dtype, xk_dev, n)) return rc;
-    if (!post_dev || !g_dev || !prob_dev || !values_dev || !out_dev) return fail(MTREE_EINVAL, "mtree_predict: null pointer");
-    if ((uintptr_t)post_dev % 8 || (uintptr_t)g_dev % 8 || (uintptr_t)prob_dev % 8 || (uintptr_t)values_dev % 8 ||
-        (uintptr_t)out_dev % 8)
-        return fail(MTREE_EINVAL, "mtree_predict: misaligned pointer");
+    if (!post_dev || !g_dev || !prob_dev || !values_dev || !out_dev) return g_err.fail(MTREE_EINVAL, "mtree_predict: null pointer");
+    if (any_misaligned(8, post_dev, g_dev, prob_dev, values_dev, out_dev))
+        return g_err.fail(MTREE_EINVAL, "mtree_predict: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     const int C = family == MTREE_BERNOULLI ? 2 : family == MTREE_CATEGORICAL ? degree : 1;
-    hipLaunchKernelGGL(values_kernel, dim3(grid_of(F.n_nodes)), dim3(kThreads), 0, st, F.n_nodes, family, degree, mode, c.np, C,
-                       post_dev, values_dev);
-    if (int rc = launched("values_kernel launch")) return rc;
-#define MTREE_PREDICT(TC, TK)                                                                                               \
-    hipLaunchKernelGGL((predict_kernel<TC, TK>), dim3(grid_of(n)), dim3(kThreads), 0, st, F, mode, C, (const TC*)xc_dev, \
-                       (const TK*)xk_dev, n, g_dev, prob_dev, (const double*)values_dev, out_dev)
+    hipLaunchKernelGGL(values_kernel, dim3(grid_of(F.n_nodes, kThreads)), dim3(kThreads), 0, st, F.n_nodes, family, degree, mode,
+                       c.np, C, post_dev, values_dev);
+    if (int rc = g_err.launched("values_kernel launch")) return rc;
+#define MTREE_PREDICT(TC, TK)                                                                                   \
+    hipLaunchKernelGGL((predict_kernel<TC, TK>), dim3(grid_of(n, kThreads)), dim3(kThreads), 0, st, F, mode, C, \
+                       (const TC*)xc_dev, (const TK*)xk_dev, n, g_dev, prob_dev, (const double*)values_dev, out_dev)
     MTREE_DISPATCH(xc_dtype, xk_dtype, MTREE_PREDICT);
 #undef MTREE_PREDICT
-    return launched("predict_kernel launch");
+    return g_err.launched("predict_kernel launch");
 }
 
 }  // extern "C"

@@ -1,10 +1,11 @@
-// What the two translation units of include/regvb.h share: the thread-local error message and the tile dispatch.
+// What the two translation units of include/regvb.h share: the thread-local error slot and the tile dispatch.
 #pragma once
 #include "../../include/regvb.h"
+#include "entry.h"
 #include "regvb_kernels.h"
 
 namespace regvb {
-int fail(int code, const char* what, hipError_t e = hipSuccess);      // sets the thread-local message (regvb_stats.hip)
+extern thread_local entry::Err g_err;      // behind regvb_last_error() (regvb_stats.hip)
 
 // f(std::integral_constant<int, T>) for the even tile count T = even_tiles(D), D <= 256
 template <typename F>

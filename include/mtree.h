@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MTREE_ABI_VERSION 1
+#define MTREE_ABI_VERSION 2
 #define MTREE_MAX_TREES 1024
 #define MTREE_MAX_NODES 4096
 #define MTREE_MAX_CHILDREN 16
@@ -100,11 +100,9 @@ int mtree_route(const mtree_forest* f, int xc_dtype, const void* xc_dev, int xk_
  * integer atomics (exact, order-free).  Real columns use no floating-point atomics and are bit-reproducible: a wave owns a
  * contiguous slab of rows of one tree and a table only it writes, adds the lanes that share a node in fixed lane order, and
  * the slabs are added in slab order.  Normal takes two passes and no pivot that nodes would share: the first sums y per stop
- * node, the second sums r = y - mu and r^2 about the node's own mu = (sum y) / n, and leaves [sum y, sum r, sum r^2].
- * pivot_dev: NULL or an 8-byte aligned pointer; it is not read (the place of the batch-wide pivot the signature once took). */
-int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev,
-                 const double* pivot_dev, int64_t n, int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev,
-                 void* stream);
+ * node, the second sums r = y - mu and r^2 about the node's own mu = (sum y) / n, and leaves [sum y, sum r, sum r^2]. */
+int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* stop_dev, const void* y_dev, int64_t n,
+                 int n_slabs, int64_t* stat_int_dev, double* stat_real_dev, void* work_dev, void* stream);
 
 /* One launch, a workgroup per tree, depth by depth from the deepest to the root.  In place: the statistics become subtree
  * totals (children added in child order).  A normal node carries [mu, c, SS]: its mean is mu + c / n, formed once, at the
@@ -115,10 +113,10 @@ int mtree_reduce(const mtree_forest* f, int family, int degree, const int32_t* s
  * lml_dev[node] = the family's log marginal likelihood of the folded posterior against h0_dev[n_post], and an inner node
  * g <- exp(t1 - L), t1 = ln g + sum of the children's L, L = logaddexp(ln(1 - g) + lml, t1); g = 0 and g = 1 are fixed
  * points.  lcm_dev[c] = the L (0.0 for an empty child) that the visited parent of node c took for it, the reference's
- * log_children_marginal_likelihood.  lnp_dev[b] += L of the root.  pivot_dev: as in mtree_reduce, not read. */
+ * log_children_marginal_likelihood.  lnp_dev[b] += L of the root. */
 int mtree_sweep(const mtree_forest* f, int family, int degree, int64_t* stat_int_dev, double* stat_real_dev,
-                const double* pivot_dev, const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev,
-                double* lcm_dev, double* lnp_dev, void* work_dev, void* stream);
+                const double* h0_dev, double* post_dev, double* g_dev, double* lml_dev, double* lcm_dev, double* lnp_dev,
+                void* work_dev, void* stream);
 
 /* values_dev[n_nodes][C] is filled from the posteriors (per node, once per call), then every row's walk in every tree is
  * folded bottom-up, value(v) = (1 - g_v) p_v + g_v value(child), p_stop at the node where the walk stops, and the trees are

@@ -4,7 +4,6 @@ import ctypes
 import json
 import os
 import pickle
-import re
 import warnings
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 
 import contexttree_oracle as orc
 import fake_contexttree_engine as fake
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
 
 NAMES = [c["name"] for c in orc.CASES]
 
@@ -251,17 +250,6 @@ def test_engine_limit_and_no_gpu():
             ct.LearnModel(2, 2).update_posterior(np.array([0, 1, 1]))
         with pytest.raises(EngineUnavailableError):
             _ctree.CtreePass(2, 2)
-
-
-def test_symbol_table_equals_header():
-    from bayesml_amd import _ctree
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ctree.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(ctree_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_ctree.SYMBOLS) == declared
-    lib = _ctree.load_library()
-    assert lib.ctree_abi_version() == 1
-    gm = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gmmvb.h")).read(), flags=re.S)
-    assert "ctree_" not in gm
 
 
 def test_sizes_and_argument_errors_without_a_gpu():

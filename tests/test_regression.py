@@ -363,24 +363,6 @@ def test_no_cpu_fallback():
 
 
 # ---- the C ABI without a GPU -----------------------------------------------------------------------------------------------
-def test_regvb_symbols_load_and_match_the_header():
-    import re
-    from conftest import ROOT
-    from bayesml_amd import _regression
-    text = open(os.path.join(ROOT, "include", "regvb.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(regvb_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_regression.SYMBOLS) == declared, "ctypes table and header disagree"
-    lib = _regression.load_library()
-    for name in declared:
-        assert getattr(lib, name) is not None
-    assert lib.regvb_abi_version() == 1 and lib.gmmvb_abi_version() == 8
-    assert lib.regvb_stats_len(128) == 128 * 128 + 128 + 2
-    assert lib.regvb_stats_len(0) == -1 and lib.regvb_stats_len(257) == -1
-    assert lib.regvb_stats_work_len(128) > 0 and lib.regvb_predict_work_len(256) == 128 * 16 * 17
-    assert lib.regvb_stats_work_len(300) == -1 and lib.regvb_predict_work_len(0) == -1
-
-
 def test_regvb_argument_errors_without_a_gpu():
     """Pure argument validation returns error codes before anything touches a device."""
     from bayesml_amd import _regression
