@@ -361,6 +361,68 @@ def test_boundary_vectors_by_forgetting(K, D, flat, monkeypatch):
     assert abs(ref["lnc"] - got["lnc"]) <= 1e-11 * abs(ref["lnc"])
 
 
+HOLD_OFF = [
+    # up to 64 states: chunks of 32, 64, 128 (two stages) and 256 steps, each doubled after a pass that did not stand; then
+    # a hold of 8 calls, one more try, and a hold of 16 begins
+    (5, 2, 40001, [1, 1, 1, 1] + [-1] * 8 + [1, -1]),
+    # 65 .. 128 states: one chunk length; holds of 8 and 16 calls between the tries
+    (72, 4, 40001, [1] + [-1] * 8 + [1] + [-1] * 16 + [1]),
+    # more than 128 states: chunks of 256 steps, the same count-down
+    (150, 3, 20001, [1] + [-1] * 8 + [1, -1]),
+]
+
+
+@pytest.mark.parametrize("K,D,T,want", HOLD_OFF)
+def test_hold_off_schedule(K, D, T, want, monkeypatch):
+    """Flat emissions and a sticky chain (the recipe of test_boundary_vectors_by_forgetting): no forgetting pass stands, and
+    hmmvb_last_boundary_pass over consecutive calls on one workspace IS the hold-off schedule - which calls try the pass (1: it
+    ran, the exact path behind it) and which are held off (-1) - for each of the three state-count ranges.  Whatever the
+    call did, its results are those of the exact path alone (GMMVB_HMM_FORGETTING_OFF)."""
+    from bayesml_amd import _kside
+    from bayesml_amd._engine import DataPass
+    dev = torch.device("cuda", 0)
+    x, _ = orc.synth_hmm(K, D, T, np.float32, seed=11)
+    rng = np.random.default_rng(13)
+    t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)   # noqa: E731
+    m = t(x[rng.integers(0, T, K)].astype(np.float64))
+    w_inv = t(np.broadcast_to(np.eye(D) * (D + 3.0) * 4000.0, (K, D, D)).copy())
+    f = _kside.features(_kside.PostT(torch.ones(K, dtype=torch.float64, device=dev), m, t(np.full(K, 2.0)),
+                                     t(np.full(K, D + 3.0)), w_inv))
+    c = (f.e_ln_lambda_det - D * _kside.LN_2PI - D / f.kappa) / 2.0
+    a = t(np.eye(K) * 0.9999 + (1.0 - 0.9999) / K)
+    pi = t(rng.dirichlet(np.ones(K)))
+    xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def run(forgetting, calls):
+        if forgetting:
+            monkeypatch.delenv("GMMVB_HMM_FORGETTING_OFF", raising=False)
+        else:
+            monkeypatch.setenv("GMMVB_HMM_FORGETTING_OFF", "1")
+        eng = DataPass(K, D, xd.dtype, T, dev)
+        eng.set_pivot(xd[:4096].to(torch.float64).mean(dim=0))
+        eng.prepare_rows(xd)
+        eng.enable_hmm()
+        eng.set_params(c, f.m, f.u)
+        how = []
+        for _ in range(calls):
+            eng.estep(xd)
+            ms, g0, gl, lnc = eng.forward_backward(pi, a)
+            how.append(eng.last_boundary_pass())
+        out = dict(ms=ms.clone(), g0=g0.clone(), gl=gl.clone(), lnc=float(lnc))
+        eng.close()
+        return out, how
+
+    ref, how0 = run(False, 1)
+    got, how1 = run(True, len(want))
+    print("hold-off schedule", (K, D, T), how1)
+    assert how0 == [-1]
+    assert how1 == want, how1
+    for k in ("ms", "g0", "gl"):
+        scale_k = max(1.0, float(ref[k].abs().max()))
+        assert float((ref[k] - got[k]).abs().max()) <= 1e-10 * scale_k, k
+    assert abs(ref["lnc"] - got["lnc"]) <= 1e-11 * abs(ref["lnc"])
+
+
 def test_forgetting_gate_sees_an_unreachable_state(monkeypatch):
     """Round-4 advisor's counter-example to an ABSOLUTE boundary test: two states, a~_01 = 1e-40 (exp(psi(0.01)) ~ 1e-44 is
     reachable with a sparse h0_zeta prior), a~_10 = 0.02, emission means 0 and 0.8.  The exact alpha_t(1) is ~1e-40 while the
