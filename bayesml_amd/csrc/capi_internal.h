@@ -11,6 +11,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "aux_kernels.h"
 #include "generic.h"
@@ -23,8 +24,18 @@ using namespace gmmvb;
 #define GMMVB_T1_SPLITS 24
 #endif
 
-extern "C" {
+// f(std::integral_constant<int, W>) for W = the mask words of K components, 1 .. 4 (K <= 256), as a compile-time constant
+template <int W = 1, typename F>
+static inline void dispatch_mask_words(int K, F&& f) {
+    if constexpr (W < 4) {
+        if ((K + 63) / 64 == W) return f(std::integral_constant<int, W>{});
+        return dispatch_mask_words<W + 1>(K, f);
+    } else {
+        return f(std::integral_constant<int, 4>{});
+    }
+}
 
+extern "C" {
 
 // profiling spans (gmmvb_profile_spans): HIP events on the launch stream around groups of kernels
 enum { kSpanEstepMain = 0, kSpanSelect = 1, kSpanGather = 2, kSpanLse = 3, kSpanLists = 4, kSpanMstepMain = 5,
@@ -62,6 +73,33 @@ static inline void span_end(gmmvb_workspace* ws, hipStream_t st) {
     ++ws->n_spans;
 }
 static inline bool phase_events(const gmmvb_workspace* ws) { return ws->prof && !ws->prof_light; }
+
+// ---- expressions and launch groups the passes share ---------------------------------------------------------------------
+// the centred copy (gmmvb_prepare_rows) is of this matrix / the digit planes exist and are of this matrix
+static inline bool xc_is_of(const gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_rows) {
+    return ws->xc_src == x_dev && ws->xc_rows == n_rows && ws->xc_ldx == ldx;
+}
+static inline bool xq_is_of(const gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_rows) {
+    return ws->xq != nullptr && ws->xq_src == x_dev && ws->xq_rows == n_rows && ws->xq_ldx == ldx;
+}
+// Per-component lists from masks and their block counts: the counts become block bases and list lengths (ws->counts), then
+// every selection block fills its part of ws->lists.  block_total: bits per block if the producer counted them (a block
+// without any is skipped); lock / lcomp: the signed delta lists of the cache of settled rows (fill_lists_kernel).
+static inline void scan_and_fill(gmmvb_workspace* ws, hipStream_t st, const unsigned long long* masks, int* blk, int nblk,
+                                 int64_t n_rows, int K, const double* block_total = nullptr, unsigned char* lock = nullptr,
+                                 const unsigned char* lcomp = nullptr) {
+    launch_scan_counts(st, blk, nblk, K, ws->counts, ws->scan_parts);
+    hipLaunchKernelGGL(fill_lists_kernel, dim3(nblk), dim3(kSelRows), 0, st, masks, ws->npad, n_rows, K, blk, ws->lists, ws->npad,
+                       lock, lcomp, block_total);
+}
+// the stateless table's argument block (project.h) over the workspace's records, masks and digit planes
+static inline ProjectArgs project_args(const gmmvb_workspace* ws, int64_t n_rows, unsigned char* lock, unsigned long long* pmask,
+                                       int proof_all, int own_fresh) {
+    return ProjectArgs{ws->xq, ws->xqe, ws->gimg, ws->gconst, ws->tile_ref, ws->lnrho, ws->npad, n_rows, ws->K, ws->D, ws->drift,
+                       ws->cvec, ws->rec_k, ws->rec_d, ws->rec_B, ws->rec_exact, ws->rec_sel, ws->rec_flags, ws->masks, ws->blk,
+                       ws->epart, ws->opart, lock, ws->dlock, ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all, own_fresh,
+                       ws->exit_ctr + 2};
+}
 
 // ---- the scratch of a tile group (workspace.h: gmmvb_scratch) -----------------------------------------------------------
 // `w` loses the buffers to another workspace of its group: its E-step output, lists and centred copy are gone.  What it

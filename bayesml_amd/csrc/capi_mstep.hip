@@ -89,7 +89,7 @@ int gmmvb_mstep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
     int64_t rows_per_split = round_up((n_rows + S - 1) / S, 64);
     if (ws->split_rows && rows_per_split > ws->split_rows) rows_per_split = ws->split_rows;
     S = (n_rows + rows_per_split - 1) / rows_per_split;
-    bool pre = ws->xc && ws->xc_src == x_dev && ws->xc_rows == n_rows && ws->xc_ldx == ldx;
+    bool pre = ws->xc && xc_is_of(ws, x_dev, ldx, n_rows);
     if (ws->wide && !pre && ws->xc) {
         // past 8 feature tiles the M-step only exists over the centred copy: made here if the caller has not
         // (multivariate_normal.LearnModel's one-pass moments call gmmvb_mstep straight after gmmvb_load_responsibilities)
@@ -176,10 +176,9 @@ int gmmvb_mstep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
             // the rows that settled or came loose in this pass (rec_finish_kernel's delta masks) enter / leave the
             // cache of settled rows - before the pass's own lists are built in the same buffers
             span_begin(ws, kSpanLists, st);
-            launch_scan_counts(st, ws->dblk, nblk, ws->K, ws->counts, ws->scan_parts);
             // (qpart: the delta and M-step pairs rec_finish_kernel counted per block - none of either: nothing to fill)
-            hipLaunchKernelGGL(fill_lists_kernel, dim3(nblk), dim3(kSelRows), 0, st, ws->dmask, ws->npad, n_rows, ws->K,
-                               ws->dblk, ws->lists, ws->npad, ws->lock, ws->lcomp, ws->e_state == 1 ? ws->qpart : nullptr);
+            scan_and_fill(ws, st, ws->dmask, ws->dblk, nblk, n_rows, ws->K, ws->e_state == 1 ? ws->qpart : nullptr, ws->lock,
+                          ws->lcomp);
             span_end(ws, st);
             MstepListArgs ld = la0;
             ld.direct_r = 3;
@@ -207,9 +206,7 @@ int gmmvb_mstep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
                 if (ws->mlists_lost)
                     return fail(GMMVB_ESTATE, "the M-step's lists were used by a read-out of settled rows: call gmmvb_estep again");
                 span_begin(ws, kSpanLists, st);
-                launch_scan_counts(st, ws->mblk, nblk, ws->K, ws->counts, ws->scan_parts);
-                hipLaunchKernelGGL(fill_lists_kernel, dim3(nblk), dim3(kSelRows), 0, st, ws->mmask, ws->npad, n_rows, ws->K,
-                                   ws->mblk, ws->lists, ws->npad, nullptr, nullptr, ws->e_state == 1 ? ws->qpart : nullptr);
+                scan_and_fill(ws, st, ws->mmask, ws->mblk, nblk, n_rows, ws->K, ws->e_state == 1 ? ws->qpart : nullptr);
                 e = hipGetLastError();
                 span_end(ws, st);
                 if (e != hipSuccess) return fail(GMMVB_EHIP, "active-sample lists", e);
@@ -218,9 +215,7 @@ int gmmvb_mstep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
             }
         } else if (!ws->active_lists) {
             span_begin(ws, kSpanLists, st);
-            launch_scan_counts(st, ws->blk, nblk, ws->K, ws->counts, ws->scan_parts);
-            hipLaunchKernelGGL(fill_lists_kernel, dim3(nblk), dim3(kSelRows), 0, st, ws->masks, ws->npad, n_rows, ws->K,
-                               ws->blk, ws->lists, ws->npad);
+            scan_and_fill(ws, st, ws->masks, ws->blk, nblk, n_rows, ws->K);
             e = hipGetLastError();
             span_end(ws, st);
             if (e != hipSuccess) return fail(GMMVB_EHIP, "active-sample lists", e);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tri_index.h"
+
 namespace gmmvb {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -26,10 +28,6 @@ constexpr double kRelevanceNats = kRelevanceBits * 0.69314718055994530942;
 constexpr int kTile = 16;      // v_mfma_f64_16x16x4_f64 output tile
 constexpr int kWave = 64;      // CDNA wavefront
 constexpr int kMaxTiles = 8;   // D <= 128
-
-__host__ __device__ constexpr int tri_pairs(int t) { return t * (t + 1) / 2; }
-// index of the tile pair (hi, lo) with lo <= hi in the packed lower triangle
-__host__ __device__ constexpr int pair_index(int hi, int lo) { return hi * (hi + 1) / 2 + lo; }
 
 // D = A(16x4) * B(4x16) + C, f64.  Lane l supplies A[l&15][l>>4] and B[l>>4][l&15]; it receives
 // C[(l>>4) + 4*r][l&15] in element r (guide: "f64 MFMA does NOT use the f32 row map").

@@ -11,7 +11,7 @@
 // measured follow their sibling on the same pipe (exact pairs and list M-step: the dense f64 kernels; proof pairs: the int8
 // bound pass).  gmmvb_policy_table reads the table.
 #pragma once
-#include "common.h"
+#include "tri_index.h"
 
 namespace gmmvb {
 

@@ -7,21 +7,10 @@
 
 #include <cstdlib>
 
-#include "policy.h"
+#include "pass_plan.h"
 
 struct gmmvb_hmm_state;      // HMM forward-backward buffers (hmm_capi.hip), allocated by hmmvb_enable
 struct gmmvb_workspace;
-
-// What an E-step leaves for the policy of the next one (and for gmmvb_last_work)
-struct gmmvb_pass_counters {
-    bool valid = false;
-    double act = 0.0, eval = 0.0, over = 0.0, settled = 0.0, listed = 0.0, accum = 0.0, proof = 0.0, exits = 0.0, moved = 0.0;
-    double cols = -1.0;          // (tile, component) columns of the bound array the last sweep went through; -1: not a lazy sweep
-    double left = -1.0;          // pairs the stateless table (project.h) did not clear; -1: the pass was no projected sweep
-    double rows = 0.0;           // rows the counters were taken over
-    double ranks = 1.0;          // ranks they were summed over
-    int mode = 0;                // kind of the pass: 0 dense, 1 bound pass, 2 carried records, 3 sweep
-};
 
 // Buffers that only live from an E-step to the M-step (or read-out) behind it: ln rho [K][npad] f64, the sample lists
 // [K][npad] i32, the centred f64 copy of the rows and the M-step's slabs - 3.5 KB per row at K = 256, D = 64, two thirds of
@@ -59,13 +48,7 @@ struct gmmvb_workspace {
     double* pivot_i8 = nullptr;        // [D] the pivot those images (and the sample digits) are centred on
     unsigned char* img_i8b = nullptr;  // [K][img_i8b_len] 3-digit images of the pruned E-step's bound pass
     int img_i8b_len = 0;
-    // output blocks the int8 bound pass evaluates (fewer blocks: cheaper pass, looser bound, more candidates for the
-    // exact pass).  tb_cand[L] = candidates per pair the last pass at level L left, tb_seen[L] = pruned E-steps since
-    // (levels not seen for 32 passes count as unknown); gmmvb_estep picks the level with the lowest modelled cost
-    int bound_tb = 0;
-    double tb_cand[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
-    double tb_act[5] = {0.0, 0.0, 0.0, 0.0, 0.0};      // active pairs per pair when tb_cand[L] was observed
-    int tb_seen[5] = {0, 0, 0, 0, 0};
+    gmmvb::BoundLevel bound;           // output blocks the int8 bound pass evaluates, and what the last passes at each level left (pass_plan.h)
     // carrying the E-step over a parameter update (gmmvb_set_drift, records.h): gamma / delta / Gamma of the pending
     // update, whether the records belong to the parameters of the last E-step on `bounds_rows` rows of `bounds_x`
     double* drift = nullptr;           // [4][K]: gamma, delta, c of the last E-step, Gamma
