@@ -19,6 +19,71 @@ int fail(int code, const char* what, hipError_t e) {
 }
 }  // namespace gmmvb
 
+namespace {
+// the sizes workspace_plan.h needs from the kernels' translation units, for K components of D features
+KernelSizes kernel_sizes(int K, int D) {
+    KernelSizes ks;
+    ks.max_tiles = kMaxTiles;
+    ks.t1_splits = GMMVB_T1_SPLITS;
+    ks.sel_rows = kSelRows;
+    ks.lse_rows = kLseRows;
+    ks.scan_parts = kScanParts;
+    ks.rec_slots = kRecSlots;
+    ks.generic_rows = generic_rows(D);
+    if (D > 32 * kMaxTiles) return ks;
+    const int T = feature_tiles(D, kMaxTiles);
+    ks.mstep_components_per_wg = mstep_components_per_wg(T, false);
+    ks.slab_len = slab_len(T);
+    ks.estep_image_doubles = estep_image_doubles(T);
+    ks.estep_tri_image_doubles = estep_tri_image_doubles();
+    ks.estep_bound_blocks = estep_bound_blocks(T);
+    ks.estep_i8_image_bytes = estep_i8_image_bytes(D, 0);
+    ks.estep_i8_bound_image_bytes = estep_i8_image_bytes(D, 1);
+    ks.estep_i8_digit_row_bytes = estep_i8_digit_row_bytes(D);
+    ks.proj_image_len = proj_image_len(K, D);
+    ks.proj_const_len = proj_const_len(K);
+    return ks;
+}
+
+// where the workspace keeps the pointer of each buffer of workspace_plan.h: the field of the same name
+struct Slots {
+    void** at[kBufCount];
+#define GMMVB_X(name) (void**)&ws->name,
+    explicit Slots(gmmvb_workspace* ws) : at{GMMVB_WORKSPACE_BUFFERS(GMMVB_X)} {}
+#undef GMMVB_X
+};
+
+struct HipAllocator {
+    hipError_t err = hipSuccess;
+    void* get(int64_t bytes, bool pinned) {
+        void* p = nullptr;
+        err = pinned ? hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault) : hipMalloc(&p, (size_t)bytes);
+        return err == hipSuccess ? p : nullptr;
+    }
+    bool zero(void* p, int64_t bytes, bool pinned) {
+        if (pinned) std::memset(p, 0, (size_t)bytes);
+        else err = hipMemset(p, 0, (size_t)bytes);
+        return err == hipSuccess;
+    }
+    void release(void* p, bool pinned) { (void)(pinned ? hipHostFree(p) : hipFree(p)); }
+};
+
+// the events, and what the kernels need set before their first launch
+hipError_t init_workspace(gmmvb_workspace* ws) {
+    hipError_t e = hipEventCreateWithFlags(&ws->ctr_ev, hipEventDisableTiming);
+    if (ws->generic) {
+        const int lds = (int)((size_t)ws->D * generic_rows(ws->D) * sizeof(double));
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)estep_generic_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)estep_generic_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        return e;
+    }
+    // the policy table at this shape, and the events its calibration records around the workspace's own first bulk passes
+    ws->pt.init(ws->T, estep_bound_blocks(ws->T) ? (ws->D + 31) / 32 : 0);
+    for (int i = 0; i < 6 && e == hipSuccess && ws->prune != 0; ++i) e = hipEventCreate(&ws->cal_ev[i]);
+    return e;
+}
+}  // namespace
+
 extern "C" {
 
 int gmmvb_abi_version(void) { return GMMVB_ABI_VERSION; }
@@ -42,231 +107,26 @@ static int create_workspace(int K, int D, int x_dtype, int64_t max_rows, gmmvb_w
     if (e != hipSuccess) return fail(GMMVB_EHIP, "hipGetDeviceProperties", e);
 
     gmmvb_workspace* ws = new (std::nothrow) gmmvb_workspace();
-    if (!ws) return fail(GMMVB_ENOMEM, "host allocation failed");
-    if (first) {
-        ws->scratch = first->scratch;
-        ++ws->scratch->refs;
-    } else {
-        ws->scratch = new (std::nothrow) gmmvb_scratch();
-        if (!ws->scratch) {
-            delete ws;
-            return fail(GMMVB_ENOMEM, "host allocation failed");
-        }
-        ws->scratch->refs = 1;
+    gmmvb_scratch* group = first ? first->scratch : new (std::nothrow) gmmvb_scratch();
+    if (!ws || !group) {
+        delete ws;
+        if (!first) delete group;
+        return fail(GMMVB_ENOMEM, "host allocation failed");
     }
-    ws->K = K;
-    ws->D = D;
-    ws->T = (D + 15) / 16;
-    // 128 < D <= 256 (round 4): dense MFMA kernels of their own - the E-step streams U's block rows through LDS
-    // (estep_rows.h), the M-step spreads a component's tile pairs over T / 2 waves (mstep.h) - instantiated for even tile
-    // counts: an odd one is rounded up (zero padded images and centred rows).  No pruning, no lists, K-side through torch.
-    ws->wide = D > 16 * kMaxTiles && D <= 32 * kMaxTiles;
-    if (ws->wide) ws->T = 2 * ((ws->T + 1) / 2);
-    ws->x_dtype = x_dtype;
-    ws->max_rows = max_rows;
-    ws->npad = round_up(max_rows, 64);
-    ws->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (D > 32 * kMaxTiles) {
-        // more than 16 feature tiles: the plain f64 kernels of generic.h (no parameter images, no pruning, no lists)
-        ws->generic = true;
-        ws->sparse = false;
-        ws->prune = 0;
-        ws->sort_rows = false;
-        ws->cache_on = false;
-        ws->gen_S = (int)std::min<int64_t>(64, std::max<int64_t>(1, max_rows / 16384));
-        const int64_t tiles = tri_pairs(ws->T);
-        struct { double** p; int64_t n; } gb[] = {
-            {&ws->lnrho, (int64_t)K * ws->npad}, {&ws->lse, ws->npad}, {&ws->cvec, K}, {&ws->pivot, D},
-            {&ws->gen_u, (int64_t)K * D * D}, {&ws->gen_m, (int64_t)K * D}, {&ws->gen_first, (int64_t)ws->gen_S * K * (D + 2)},
-            {&ws->gen_second, (int64_t)ws->gen_S * K * tiles * 256}, {&ws->ctr, 8}};
-        for (auto& b : gb) {
-            e = hipMalloc((void**)b.p, (size_t)b.n * sizeof(double));
-            if (e != hipSuccess) {
-                gmmvb_workspace_destroy(ws);
-                return fail(GMMVB_ENOMEM, "hipMalloc (workspace)", e);
-            }
-            ws->bytes += b.n * (int64_t)sizeof(double);
-        }
-        ws->scratch->lnrho = ws->lnrho;            // (freed with the scratch; the generic path has no tile groups)
-        ws->scratch->npad = ws->npad;
-        e = hipMemset(ws->pivot, 0, (size_t)D * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(ws->ctr, 0, 8 * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&ws->ctr_host, 8 * sizeof(double), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ws->ctr_ev, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            const size_t lds = (size_t)D * generic_rows(D) * sizeof(double);
-            e = hipFuncSetAttribute((const void*)estep_generic_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)estep_generic_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
-        if (e != hipSuccess) {
-            gmmvb_workspace_destroy(ws);
-            return fail(GMMVB_EHIP, "workspace initialisation", e);
-        }
-        *out = ws;
-        return GMMVB_OK;
-    }
-    {
-        const int kpw = mstep_components_per_wg(ws->T, false);     // the smaller of the two forms: sizes the slabs
-        ws->KG = (K + kpw - 1) / kpw;
-    }
-    // row splits of the dense M-step: ~4 workgroups per CU; with a single feature tile a step is a row load and one
-    // MFMA - latency, not arithmetic - so many more, shorter, splits (HMM config 5)
-    ws->S_cap = (int)round_up(((int64_t)(ws->T == 1 ? GMMVB_T1_SPLITS : 4) * ws->num_cu + ws->KG - 1) / ws->KG, 8);      // (24: three of the HMM M-step's 50-KB workgroups per CU)
-    if (ws->S_cap < 8) ws->S_cap = 8;
-    {
-        // Cap on the rows of one M-step split: 16 MB of centred rows (16384 rows at D = 128).  All component groups
-        // of a split stream the same rows; short splits keep those workgroups within an L2's reach of each other
-        // (measured at C3: fetch 96 GB -> 16-21 GB ~ the algorithmic 15.4 GB, kernel 175.6 -> 171.5 ms) at the
-        // price of more slabs (+0.7 ms reduce).
-        ws->split_rows = round_up(std::max<int64_t>(64, (16 << 20) / (16 * ws->T * 8)), 64);
-        const int64_t need = round_up((max_rows + ws->split_rows - 1) / ws->split_rows, 8);
-        if (need > ws->S_cap) ws->S_cap = (int)need;
-    }
-    ws->img_len = estep_image_doubles(ws->T);
-    {
-        const char* v = dev_env("GMMVB_ESTEP_VARIANT");
-        ws->estep_variant = kEstepLds8;      // measured fastest (two waves per SIMD share one LDS image)
-        if (ws->wide) v = nullptr;           // (one E-step kernel past 8 feature tiles)
-        // ... except with a single feature tile (D <= 16): the 2.5-KB images stay in L1, staging them through LDS with a
-        // barrier per group of components only costs (HMM config 5: emission 4.4 -> 3.1 ms).  No pruning at that size anyway.
-        // (round 4) ... and with one tile the vector ALU, which can skip U's upper triangle, beats the matrix pipe (estep.h,
-        // estep_rows16_f64: HMM emission 3.1 -> 2.7 ms); GMMVB_ESTEP_VARIANT=direct keeps the MFMA kernel
-        if (ws->T == 1) ws->estep_variant = kEstepValu16;
-        if (v && std::strcmp(v, "lds8") == 0) ws->estep_variant = kEstepLds8;
-        if (v && std::strcmp(v, "direct") == 0) ws->estep_variant = kEstepDirect;
-        if (v && std::strcmp(v, "lds4") == 0) ws->estep_variant = kEstepLds;
-        if (v && std::strcmp(v, "i8") == 0) ws->estep_variant = kEstepI8;
-    }
-    if (ws->estep_variant == kEstepValu16) {
-        e = hipMalloc((void**)&ws->tri, (size_t)K * estep_tri_image_doubles() * sizeof(double));
-        if (e != hipSuccess) {
-            gmmvb_workspace_destroy(ws);
-            return fail(GMMVB_ENOMEM, "hipMalloc (packed triangular images)", e);
-        }
-        ws->bytes += (int64_t)K * estep_tri_image_doubles() * (int64_t)sizeof(double);
-    }
-    struct { double** p; int64_t n; } bufs[] = {
-        {&ws->lnrho, (int64_t)K * ws->npad}, {&ws->lse, ws->npad},
-        {&ws->img, (int64_t)K * ws->img_len},
-        {&ws->cvec, K},                      {&ws->pivot, D},
-        {&ws->slabs, (int64_t)ws->S_cap * K * slab_len(ws->T)},
-        {&ws->xc, 0},
-        {&ws->dpart, ((ws->npad + kLseRows - 1) / kLseRows) * K}, {&ws->thr, K},
-        {&ws->apart, (ws->npad + kSelRows - 1) / kSelRows}, {&ws->ctr, 8}, {&ws->drift, 4 * (int64_t)K}};
-    bufs[6].n = (ws->npad + 64) * 16 * (int64_t)ws->T;            // the centred copy
-    {
-        const char* v = std::getenv("GMMVB_MSTEP_SPARSE");         // "0" = always the dense M-step
-        ws->sparse = !(v && std::strcmp(v, "0") == 0);
-        if (max_rows > 2000000000) ws->sparse = false;             // the sample lists hold 32-bit row numbers
-        if (ws->wide) ws->sparse = false;                          // (dense kernels only past 8 feature tiles)
-        if (K == 1) {
-            // one component: r = 1 for every row, nothing to prune, list or cache - and the one-pass moment computation of
-            // multivariate_normal.LearnModel (K = 1, unit responsibilities) should not pay for a centred copy it never
-            // builds: the M-step reads x directly
-            ws->sparse = false;
-            if (!ws->wide) bufs[6].n = 0;          // (past 8 feature tiles the M-step only exists over the centred copy)
-        }
-        v = dev_env("GMMVB_SORT_ROWS");
-        ws->sort_rows = !(v && std::strcmp(v, "0") == 0) && (int64_t)max_rows <= 2000000000;
-        v = std::getenv("GMMVB_ESTEP_PRUNE");
-        ws->prune = (v && std::strcmp(v, "0") == 0) ? 0 : ((v && std::strcmp(v, "force") == 0) ? 2 : 1);
-        if (!ws->sparse || estep_bound_blocks(ws->T) == 0 || K > 256) ws->prune = 0;
-        v = dev_env("GMMVB_SETTLE_MARGIN");                    // nats; negative = never settle rows
-        if (v) ws->settle_margin = std::atof(v);
-        v = dev_env("GMMVB_PROOF");                            // "0": no int8 proof round (rows then never settle);
-        ws->opt_proof = !(v && std::strcmp(v, "0") == 0);
-        ws->opt_proof_all = !(v && std::strcmp(v, "settled") == 0);     // "settled": only the settled rows' pairs go through it
-        v = dev_env("GMMVB_PROOF_BLOCKED");                    // "0": the proof round walks component after component
-        ws->opt_proof_blocked = !(v && std::strcmp(v, "0") == 0);
-        v = dev_env("GMMVB_SWEEP_LAZY");                       // "0": every sweep reads all K bounds of every row
-        ws->opt_lazy = !(v && std::strcmp(v, "0") == 0);
-        // the stateless table of project.h - off by default (measured, profiles/r6_experiments.md: on the benchmark's fits it
-        // costs more than the proof pairs it saves): "filter" = it takes pairs off the carried sweep's proof lists, "only" =
-        // it replaces the carried per-pair bounds
-        v = dev_env("GMMVB_PROJECT");
-        ws->opt_project = (v && std::strcmp(v, "filter") == 0) ? 1 : ((v && std::strcmp(v, "only") == 0) ? 2 : 0);
-        v = dev_env("GMMVB_REGROUP_MARGIN");     // "0": the rows are regrouped by best component only
-        ws->opt_regroup_margin = !(v && std::strcmp(v, "0") == 0);
-        v = dev_env("GMMVB_GATHER_EXIT");                      // "0": candidates are always evaluated in full
-        ws->gather_exit = !(v && std::strcmp(v, "0") == 0);
-        v = dev_env("GMMVB_MSTEP_CACHE");
-        ws->cache_on = !(v && std::strcmp(v, "0") == 0);
-        ws->opt_carry_off = dev_env("GMMVB_ESTEP_CARRY_OFF") != nullptr;
-        ws->opt_hmm_mstep_dense = dev_env("GMMVB_HMM_MSTEP_DENSE") != nullptr;
-        {
-            const char* dbg = std::getenv("GMMVB_DEBUG");
-            ws->opt_debug = dbg && dbg[0] == '2';
-        }
-    }
-    {
-        const bool full = ws->estep_variant == kEstepI8, bound = ws->prune != 0;
-        hipError_t e8 = hipSuccess;
-        if (full) {
-            ws->img_i8_len = estep_i8_image_bytes(D, 0);
-            e8 = hipMalloc((void**)&ws->img_i8, (size_t)K * ws->img_i8_len);
-            ws->bytes += (int64_t)K * ws->img_i8_len;
-        }
-        if (bound && e8 == hipSuccess) {
-            ws->img_i8b_len = estep_i8_image_bytes(D, 1);
-            e8 = hipMalloc((void**)&ws->img_i8b, (size_t)K * ws->img_i8b_len);
-            ws->bytes += (int64_t)K * ws->img_i8b_len;
-        }
-        if ((full || bound) && e8 == hipSuccess) {
-            e8 = hipMalloc((void**)&ws->pivot_i8, (size_t)D * sizeof(double));
-            ws->bytes += D * (int64_t)sizeof(double);
-        }
-        if (e8 != hipSuccess) {
-            gmmvb_workspace_destroy(ws);
-            return fail(GMMVB_ENOMEM, "hipMalloc (int8 images)", e8);
-        }
-    }
-    for (auto& b : bufs) {
-        if (b.n == 0) continue;
-        const bool shared = b.p == &ws->lnrho || b.p == &ws->xc || b.p == &ws->slabs;
-        if (shared && first) continue;             // a further tile of a group: the first tile's buffers (below)
-        e = hipMalloc((void**)b.p, (size_t)b.n * sizeof(double));
-        if (e != hipSuccess) {
-            if (shared) *b.p = nullptr;
-            gmmvb_workspace_destroy(ws);
-            return fail(GMMVB_ENOMEM, "hipMalloc (workspace)", e);
-        }
-        ws->bytes += b.n * (int64_t)sizeof(double);
-    }
-    {
-        gmmvb_scratch* sc = ws->scratch;
-        if (!first) {
-            sc->lnrho = ws->lnrho;
-            sc->xc = ws->xc;
-            sc->slabs = ws->slabs;
-            sc->npad = ws->npad;
-            sc->xc_len = bufs[6].n;
-            sc->slabs_len = bufs[5].n;
-        } else {
-            if (ws->npad > sc->npad || bufs[6].n > sc->xc_len || bufs[5].n > sc->slabs_len || (bufs[6].n > 0 && !sc->xc)) {
-                gmmvb_workspace_destroy(ws);
-                return fail(GMMVB_EINVAL, "a further tile must not be larger than the group's first workspace");
-            }
-            ws->lnrho = sc->lnrho;
-            ws->xc = bufs[6].n > 0 ? sc->xc : nullptr;
-            ws->slabs = sc->slabs;
-        }
-    }
-    if (ws->sparse && K <= 256 && ensure_lists(ws) != GMMVB_OK) {      // not inside somebody's timed iteration
+    ws->scratch = group;
+    ++group->refs;
+    const KernelSizes ks = kernel_sizes(K, D);
+    const WorkspaceShape shape = make_shape(K, D, x_dtype, max_rows, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256,
+                                            WorkspaceOptions::read(std::getenv), ks);
+    static_cast<WorkspaceShape&>(*ws) = shape;
+    if (!first) group->npad = shape.npad;
+    ws->buffers = buffer_plan(shape, ks, group->npad);      // (not inside somebody's timed iteration: lists and records too)
+    HipAllocator hip;
+    if (const BufferSpec* failed = allocate_all(ws->buffers, Slots(ws).at, group, hip, &ws->bytes)) {
         gmmvb_workspace_destroy(ws);
-        return GMMVB_ENOMEM;
+        return fail(failed->code, failed->what, hip.err);
     }
-    e = hipMemset(ws->pivot, 0, (size_t)D * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(ws->ctr, 0, 8 * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ws->ctr_host, 8 * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ws->ctr_ev, hipEventDisableTiming);
-    // the policy table at this shape, and the events its calibration records around the workspace's own first bulk passes
-    ws->pt.init(ws->T, estep_bound_blocks(ws->T) ? (D + 31) / 32 : 0);
-    {
-        const char* v = dev_env("GMMVB_POLICY_CALIBRATE");
-        ws->opt_calibrate = !(v && std::strcmp(v, "0") == 0);
-    }
-    for (int i = 0; i < 6 && e == hipSuccess && ws->prune != 0; ++i) e = hipEventCreate(&ws->cal_ev[i]);
+    e = init_workspace(ws);
     if (e != hipSuccess) {
         gmmvb_workspace_destroy(ws);
         return fail(GMMVB_EHIP, "workspace initialisation", e);
@@ -292,36 +152,19 @@ int gmmvb_workspace_create_tile(gmmvb_workspace* first, int64_t max_rows, gmmvb_
 
 int gmmvb_workspace_destroy(gmmvb_workspace* ws) {
     if (!ws) return GMMVB_OK;
-    release_scratch(ws);
-    double* bufs[] = {ws->lnrho, ws->lse, ws->img, ws->tri, ws->cvec, ws->pivot, ws->slabs, ws->xc, ws->dpart, ws->thr,
-                      ws->apart, ws->ctr, ws->drift, ws->epart, ws->opart, ws->mpart, ws->gen_u, ws->gen_m, ws->gen_first,
-                      ws->gen_second};
-    int* ibufs[] = {ws->lists, ws->khat, ws->counts, ws->blk, ws->scan_parts, ws->plan, ws->plan_m, ws->perm, ws->iperm, ws->perm_tmp};
-    if (ws->xp) (void)hipFree(ws->xp);
-    void* rbufs[] = {ws->rec_k, ws->rec_d, ws->rec_B, ws->rec_exact, ws->rec_sel, ws->rec_flags, ws->ub32,
-                     ws->lock, ws->lcomp, ws->dlock, ws->rthr, ws->exit_ctr, ws->dmask, ws->dblk, ws->mmask, ws->mblk, ws->cache, ws->spart, ws->gpart, ws->qpart,
-                     ws->rmask, ws->rblk, ws->xq, ws->xqe, ws->ppart, ws->tmeta, ws->gimg, ws->gconst, ws->tile_ref};
-    for (void* p : rbufs)
-        if (p) (void)hipFree(p);
-    if (ws->ctr_host) (void)hipHostFree(ws->ctr_host);
-    if (ws->pol_host) (void)hipHostFree(ws->pol_host);
-    if (ws->pol_ev) (void)hipEventDestroy(ws->pol_ev);
-    if (ws->exit_host) (void)hipHostFree(ws->exit_host);
-    if (ws->ctr_ev) (void)hipEventDestroy(ws->ctr_ev);
-    for (int* p : ibufs)
-        if (p) (void)hipFree(p);
-    if (ws->masks) (void)hipFree(ws->masks);
-    for (double* p : bufs)
-        if (p) (void)hipFree(p);
-    if (ws->img_i8) (void)hipFree(ws->img_i8);
-    if (ws->img_i8b) (void)hipFree(ws->img_i8b);
-    if (ws->pivot_i8) (void)hipFree(ws->pivot_i8);
-    for (hipEvent_t e : ws->ev)
+    gmmvb_scratch* group = ws->scratch;
+    if (group && group->owner == ws) group->owner = nullptr;
+    HipAllocator hip;
+    if (free_all(ws->buffers, Slots(ws).at, group, hip)) delete group;
+    if (ws->pol_host) (void)hipHostFree(ws->pol_host);      // (gmmvb_set_shard)
+    auto drop = [](hipEvent_t e) {
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ws->span_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ws->cal_ev)
-        if (e) (void)hipEventDestroy(e);
+    };
+    drop(ws->pol_ev);
+    drop(ws->ctr_ev);
+    for (hipEvent_t e : ws->ev) drop(e);
+    for (hipEvent_t e : ws->span_ev) drop(e);
+    for (hipEvent_t e : ws->cal_ev) drop(e);
     if (ws->hmm) hmm_state_destroy(ws->hmm);
     delete ws;
     return GMMVB_OK;
@@ -583,94 +426,6 @@ int gmmvb_set_params(gmmvb_workspace* ws, const double* c_dev, const double* m_d
     }
     ws->have_params = true;
     ws->params_used = false;
-    return GMMVB_OK;
-}
-
-// sample lists of the pruned E-step and the sparse M-step, candidate records, gather plan, per-block counters
-int ensure_lists(gmmvb_workspace* ws) {
-    if (ws->lists) return GMMVB_OK;
-    const int64_t sel_blocks = (ws->npad + kSelRows - 1) / kSelRows, words = (ws->K + 63) / 64;
-    const int64_t np = ws->npad;
-    hipError_t e = hipSuccess;
-    const bool own_lists = ws->scratch->lists == nullptr;
-    if (own_lists) {                   // one set for the tile group, sized for its first (largest) workspace
-        e = hipMalloc((void**)&ws->scratch->lists, (size_t)ws->K * ws->scratch->npad * sizeof(int));
-        if (e != hipSuccess) ws->scratch->lists = nullptr;
-    }
-    if (e == hipSuccess) ws->lists = ws->scratch->lists;
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->khat, (size_t)np * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->counts, (size_t)ws->K * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->plan, (size_t)(ws->K + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->plan_m, (size_t)(ws->K + 2) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->blk, (size_t)sel_blocks * ws->K * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->scan_parts, (size_t)ws->K * kScanParts * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->masks, (size_t)words * np * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->lock, (size_t)np);
-    if (e == hipSuccess) e = hipMemset(ws->lock, 0, (size_t)np);
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->lcomp, (size_t)np);
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->dlock, (size_t)np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rthr, (size_t)np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->exit_ctr, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(ws->exit_ctr, 0, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ws->exit_host, 4 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess) ws->exit_host[0] = ws->exit_host[1] = ws->exit_host[2] = ws->exit_host[3] = 0;
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->dmask, (size_t)words * np * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->dblk, (size_t)sel_blocks * ws->K * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->mmask, (size_t)words * np * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rmask, (size_t)words * np * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rblk, (size_t)sel_blocks * ws->K * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->mblk, (size_t)sel_blocks * ws->K * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->cache, (size_t)gmmvb_stats_len(ws->K, ws->D) * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(ws->cache, 0, (size_t)gmmvb_stats_len(ws->K, ws->D) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->spart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->gpart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->qpart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->epart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->opart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->mpart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->ppart, (size_t)sel_blocks * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(ws->ppart, 0, (size_t)sel_blocks * sizeof(double));
-    if (ws->prune != 0 && ws->img_i8b && ws->opt_proof && ws->cache_on) {
-        const int64_t rb = estep_i8_digit_row_bytes(ws->D);
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->xq, (size_t)(np * rb));
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->xqe, (size_t)np);
-        if (e == hipSuccess) ws->bytes += np * (rb + 1);
-        // the stateless sweep's table (project.h): needs the digit planes, regrouped rows and at least two feature blocks
-        if (ws->opt_project != 0 && ws->sort_rows && ws->K <= kSelRows && ws->D > 32 && ws->D <= 128) {
-            const int64_t ib = proj_image_len(ws->K, ws->D), cl = proj_const_len(ws->K);
-            if (e == hipSuccess) e = hipMalloc((void**)&ws->gimg, (size_t)ib);
-            if (e == hipSuccess) e = hipMemset(ws->gimg, 0, (size_t)ib);
-            if (e == hipSuccess) e = hipMalloc(&ws->gconst, (size_t)cl * 16);
-            if (e == hipSuccess) e = hipMalloc((void**)&ws->tile_ref, (size_t)sel_blocks * sizeof(int));
-            if (e == hipSuccess) ws->bytes += ib + cl * 16 + sel_blocks * 4;
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_k, (size_t)kRecSlots * np * sizeof(unsigned short));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_d, (size_t)kRecSlots * np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_B, (size_t)np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_exact, (size_t)np);
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_sel, (size_t)np);
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->rec_flags, (size_t)np);
-    if (e == hipSuccess) e = hipMalloc((void**)&ws->ub32, (size_t)ws->K * np * sizeof(float));
-    if (e == hipSuccess) ws->bytes += (int64_t)ws->K * np * (int64_t)sizeof(float);
-    if (ws->opt_lazy && ws->K <= kSelRows) {       // the lazy sweep's state per tile of kSelRows rows and component
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->tmeta, (size_t)sel_blocks * ws->K * sizeof(float4));
-        if (e == hipSuccess) ws->bytes += sel_blocks * ws->K * (int64_t)sizeof(float4);
-    }
-    const size_t esz = ws->x_dtype == GMMVB_F64 ? 8 : 4;
-    if (ws->sort_rows) {
-        if (e == hipSuccess) e = hipMalloc(&ws->xp, (size_t)ws->max_rows * ws->D * esz);
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->perm, (size_t)np * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->iperm, (size_t)np * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&ws->perm_tmp, (size_t)np * sizeof(int));
-        if (e == hipSuccess) ws->bytes += (int64_t)ws->max_rows * ws->D * (int64_t)esz + 3 * np * (int64_t)sizeof(int);
-    }
-    if (e != hipSuccess) return fail(GMMVB_ENOMEM, "hipMalloc (sample lists / records)", e);
-    // lists, khat, counts, plans, four sets of block counts and their scan parts; four sets of masks; lock / lcomp / dlock /
-    // rthr; the cache; eight per-block counters; the records
-    ws->bytes += ((own_lists ? (int64_t)ws->K * ws->scratch->npad : 0) + np + 4 * ws->K + 3 + 4 * sel_blocks * ws->K + (int64_t)ws->K * kScanParts) * (int64_t)sizeof(int) +
-                 4 * words * np * 8 + np * (1 + 1 + 4 + 4) + gmmvb_stats_len(ws->K, ws->D) * 8 + 8 * sel_blocks * 8 +
-                 np * (kRecSlots * 6 + 4 + 3);
     return GMMVB_OK;
 }
 

@@ -215,7 +215,7 @@ namespace {
 // table fits the M-step's slabs (free during an E-step; estep_i8.h), else component after component.
 hipError_t proof_round(gmmvb_workspace* ws, hipStream_t st, const int* blk_base, int sel_grid, int64_t n_rows, float* ub) {
     if (ws->opt_proof_blocked && ws->slabs &&
-        estep_i8_proof_work_bytes(ws->K, n_rows) <= ws->scratch->slabs_len * (int64_t)sizeof(double))
+        estep_i8_proof_work_bytes(ws->K, n_rows) <= ws->scratch->bytes[kBuf_slabs])
         return launch_estep_i8_proof_blocked(ws->D, ws->num_cu, st, ws->xq, ws->xqe, ws->img_i8b, ws->cvec, ws->K, ws->lists,
                                              ws->npad, ws->counts, blk_base, sel_grid, ws->slabs, ub, ws->lnrho, ws->npad);
     hipLaunchKernelGGL(gather_plan_kernel, dim3(1), dim3(64), 0, st, ws->counts, ws->K, estep_i8_pairs_per_chunk(), ws->plan);
@@ -731,8 +731,6 @@ int gmmvb_estep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
     if (p.mode == kPassDense) {
         rc = p.run_dense();
     } else {
-        rc = ensure_lists(ws);
-        if (rc) return rc;
         rc = p.mode == kPassBound ? p.run_bound() : p.run_sweep();
         if (rc == GMMVB_OK) rc = p.run_candidates();
     }

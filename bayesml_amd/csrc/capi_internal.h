@@ -123,24 +123,7 @@ static inline void claim_scratch(gmmvb_workspace* ws) {
     if (s->owner) yield_scratch(s->owner);
     s->owner = ws;
 }
-static inline void release_scratch(gmmvb_workspace* ws) {
-    gmmvb_scratch* s = ws->scratch;
-    if (!s) return;
-    if (s->owner == ws) s->owner = nullptr;
-    if (--s->refs <= 0) {          // (a creation that failed half-way has not handed its buffers over yet)
-        double* d[] = {s->lnrho ? s->lnrho : ws->lnrho, s->xc ? s->xc : ws->xc, s->slabs ? s->slabs : ws->slabs};
-        for (double* p : d)
-            if (p) (void)hipFree(p);
-        if (s->lists) (void)hipFree(s->lists);
-        delete s;
-    }
-    ws->scratch = nullptr;
-    ws->lnrho = ws->xc = ws->slabs = nullptr;
-    ws->lists = nullptr;
-}
-
 // ---- defined in capi.hip
-int ensure_lists(gmmvb_workspace* ws);
 int fetch_counters(gmmvb_workspace* ws);
 void poll_counters(gmmvb_workspace* ws);
 int take_policy(gmmvb_workspace* ws);

@@ -137,8 +137,6 @@ int gmmvb_mstep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
     if (ws->lock_live && !sparse)
         return fail(GMMVB_ESTATE, "settled rows need the list M-step over the matrix of the E-step (gmmvb_prepare_rows)");
     if (sparse) {      // E-step output: only the samples that can change the f64 sums, through per-component lists
-        rc = ensure_lists(ws);
-        if (rc) return rc;
         const int nblk = (int)((n_rows + kSelRows - 1) / kSelRows);
         if (phase_events(ws)) note_hip(ws, hipEventRecord(ws->ev[2], st));      // the list building is part of the M-step's time
         const int cap_chunks0 = (int)std::min<int64_t>((int64_t)ws->S_cap * ws->K, 1 << 30);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "workspace_plan.h"      // EstepVariant
+
 struct gmmvb_hmm_state;
 
 namespace gmmvb {
@@ -19,7 +21,6 @@ struct MstepArgs {
 };
 
 // rows of x handled by one E-step workgroup for (variant, T, dtype); doubles per component parameter image
-enum EstepVariant { kEstepLds = 0, kEstepDirect = 1, kEstepLds8 = 2, kEstepI8 = 3, kEstepValu16 = 4 };
 int estep_rows_per_wg(int variant, int T, int x_is_f64);
 int estep_threads(int variant);
 int estep_image_doubles(int T);

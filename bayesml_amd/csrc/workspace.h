@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "pass_plan.h"
+#include "workspace_plan.h"
 
 struct gmmvb_hmm_state;      // HMM forward-backward buffers (hmm_capi.hip), allocated by hmmvb_enable
 struct gmmvb_workspace;
@@ -18,36 +19,22 @@ struct gmmvb_workspace;
 // tile: what a tile carries from iteration to iteration (f32 bounds, records, digit planes, settled rows, row order) stays
 // its own.  `owner` is the workspace whose E-step output the buffers hold; another workspace that needs them takes them
 // over (capi.hip: claim_scratch) and the previous owner is back to "no E-step output".  All on one stream.
-struct gmmvb_scratch {
-    double* lnrho = nullptr;
-    double* xc = nullptr;
-    double* slabs = nullptr;
-    int* lists = nullptr;
-    int64_t npad = 0;                  // rows (padded) the buffers were sized for
-    int64_t xc_len = 0, slabs_len = 0; // doubles
+struct gmmvb_scratch : gmmvb::Scratch {   // buf[kBuf_lnrho], [kBuf_xc], [kBuf_slabs], [kBuf_lists], their bytes, npad, refs
     gmmvb_workspace* owner = nullptr;
-    int refs = 0;
 };
 
-struct gmmvb_workspace {
-    int K = 0, D = 0, T = 0, x_dtype = 0;
+// K, D, T, the sizes derived from them and every switch are the shape the workspace was created as (workspace_plan.h)
+struct gmmvb_workspace : gmmvb::WorkspaceShape {
     gmmvb_scratch* scratch = nullptr;  // lnrho / xc / slabs / lists below point into it
     bool lost_estep = false;           // the last E-step's output went to another tile of the group (e_state 0); its counters,
                                        // masks and block counts are still that pass's
-    int64_t max_rows = 0, npad = 0;
-    int num_cu = 0, KG = 0, S_cap = 0;
-    int64_t split_rows = 0;    // cap on rows per M-step split
     double* lnrho = nullptr;   // [K][npad]
     double* lse = nullptr;     // [npad]
     double* img = nullptr;     // [K][img_len] parameter images (layout: estep.h)
-    int img_len = 0;
-    int estep_variant = 0;     // kEstepLds8 (default); env GMMVB_ESTEP_VARIANT=direct|lds4|i8 selects the others
     double* tri = nullptr;             // [K][estep_tri_image_doubles()] packed lower-triangular images (D <= 16: estep_rows16_f64)
     unsigned char* img_i8 = nullptr;   // [K][img_i8_len] int8-digit parameter images (estep_i8.h), variant kEstepI8 only
-    int img_i8_len = 0;
     double* pivot_i8 = nullptr;        // [D] the pivot those images (and the sample digits) are centred on
     unsigned char* img_i8b = nullptr;  // [K][img_i8b_len] 3-digit images of the pruned E-step's bound pass
-    int img_i8b_len = 0;
     gmmvb::BoundLevel bound;           // output blocks the int8 bound pass evaluates, and what the last passes at each level left (pass_plan.h)
     // carrying the E-step over a parameter update (gmmvb_set_drift, records.h): gamma / delta / Gamma of the pending
     // update, whether the records belong to the parameters of the last E-step on `bounds_rows` rows of `bounds_x`
@@ -98,7 +85,7 @@ struct gmmvb_workspace {
     // unit costs and thresholds of the pass policy at this workspace's shape (policy.h); calibration from its own first
     // dense E-step / dense M-step / bound pass: HIP events around those launches, taken over when they have completed
     gmmvb::PolicyTable pt;
-    bool opt_calibrate = true;         // gmmvb_policy_calibrate(ws, 0) / env GMMVB_POLICY_CALIBRATE=0: the scaled literals only
+    // (opt_calibrate: also gmmvb_policy_calibrate(ws, 0))
     hipEvent_t cal_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // begin / end for dense E, dense M, bound pass
     double cal_pairs[3] = {0.0, 0.0, 0.0};       // pairs behind a pending measurement (0: none pending, -1: done)
     int cal_tries[3] = {0, 0, 0};                // measurements discarded so far
@@ -118,14 +105,12 @@ struct gmmvb_workspace {
     double* pivot = nullptr;   // [D]
     double* dpart = nullptr;   // [ceil(npad / 1024)][K] block maxima of ln r (row_lse_kernel)
     double* thr = nullptr;     // [K] M-step skip thresholds: max_n ln r_nk - 80 ln 2 (valid while e_state == 1)
-    bool sparse = true;        // env GMMVB_MSTEP_SPARSE=0: always run the dense M-step
     double* apart = nullptr;   // [ceil(npad / 256)] pairs with ln r >= -80 ln 2 per selection block
     int64_t act_rows = 0;      // rows of the E-step whose active pairs were counted (0 = not counted)
     double act_host = -1.0;    // host copy of ctr[0] for that E-step (-1 = not fetched yet)
     double evaluated = 0.0;    // pairs the last E-step evaluated exactly (-1: on the device, see gmmvb_last_sparsity)
-    // pruned E-step (estep.h): env GMMVB_ESTEP_PRUNE = 0 never | force always | default: when the previous E-step
-    // over the same rows left at most half of the pairs relevant and N K >= 2^23
-    int prune = 1;
+    // pruned E-step (estep.h): `prune` 0 never | 2 always | 1: when the previous E-step over the same rows left at most half
+    // of the pairs relevant and N K >= 2^23
     int* lists = nullptr;      // [K][npad] sample lists (E-step candidates, then the M-step's active rows)
     bool active_lists = false; // the lists currently hold the active rows of the last E-step (scan + fill done)
     bool blk_fresh = false;    // blk still holds the block COUNTS of masks (not yet scanned into bases)
@@ -155,7 +140,7 @@ struct gmmvb_workspace {
     double* cache = nullptr;           // [stats_len] statistics of the settled rows
     double* spart = nullptr, *gpart = nullptr, *qpart = nullptr;   // [blocks] settled rows / listed pairs / M-step pairs per selection block
     unsigned long long* rmask = nullptr;   // read-outs of settled rows: their (row, component) pairs ...
-    int* rblk = nullptr;                   // ... and block counts (allocated by the first such read-out)
+    int* rblk = nullptr;                   // ... and block counts (allocated with the lists)
     bool lock_live = false;            // some rows may be settled: the list M-step must add the cache
     bool delta_pending = false;        // an E-step marked rows 2 / 3 / 4 and no M-step has applied them yet
     bool mlists_done = false;          // the lists hold the M-step's own lists (mmask) of the last E-step
@@ -163,12 +148,7 @@ struct gmmvb_workspace {
     bool skip_used = false;            // some pass since the cache was last emptied was allowed to settle rows
     bool lock_reset = false;           // the settled state belongs to something else now: drop it at the next E-step
     bool settled_fresh = false;        // read-outs: the settled rows' ln rho / lse were re-evaluated for the parameters in force
-    double settle_margin = 1e300;      // nats of slack demanded before a row is settled (< 0: never; 1e300: every single-component row)
-    bool cache_on = true;              // env GMMVB_MSTEP_CACHE=0: no cache of single-component rows
-    bool gather_exit = true;           // env GMMVB_GATHER_EXIT=0: no early way out in the candidate gather
-    // further switches, all read ONCE when the workspace is created (no getenv on the per-iteration path)
-    bool opt_carry_off = false;        // GMMVB_ESTEP_CARRY_OFF: ignore gmmvb_set_drift
-    bool opt_debug = false;            // GMMVB_DEBUG=2: one line per E-step on stderr
+    // (settle_margin: nats of slack demanded before a row is settled - < 0: never; 1e300: every single-component row)
     // Proof round (estep_i8.h, records.h): the three int8 digit planes of every row, in the internal row order, made with
     // the centred copy (gmmvb_prepare_rows) and again when the rows are regrouped.  Valid for the matrix xq_src while the
     // pivot they are centred on is the one the component images were packed for (xq_gen == img_gen).
@@ -177,22 +157,12 @@ struct gmmvb_workspace {
     const void* xq_src = nullptr;
     int64_t xq_rows = 0, xq_ldx = 0;
     int pivot_gen = 0, xq_gen = -1, img_gen = -2;
-    bool opt_proof = true;             // env GMMVB_PROOF=0: settled rows with candidates go straight to the f64 gather
-    bool opt_hmm_mstep_dense = false;  // env GMMVB_HMM_MSTEP_DENSE: the HMM's small M-step walks every (step, state), not only gamma >= 2^-80
-    bool opt_proof_blocked = true;     // env GMMVB_PROOF_BLOCKED=0: estep_i8_proof instead of estep_i8_proof_blocked (row superblocks)
-    bool opt_regroup_margin = true;    // env GMMVB_REGROUP_MARGIN=0: regroup by best component only (no second key: how firmly a row sits in it)
-    bool opt_lazy = true;              // env GMMVB_SWEEP_LAZY=0: every sweep goes through all K bounds of every row
-    bool opt_proof_all = true;         // the candidates of rows with an exact reference go through the proof round too (env
-                                       // GMMVB_PROOF=settled: only the settled rows' pairs)
     // The stateless sweep (project.h): bounds from the parameters in force and the rows' int8 digit planes instead of the
     // carried per-pair array.  gimg / gconst are made by gmmvb_set_params when a sweep can follow (regrouped rows, digit
     // planes about the pivot in force, a drift hint for the settled rows' own bound), tile_ref by the regrouping.
     unsigned char* gimg = nullptr;     // [K][proj_image_bytes] int8 digit images of g_jk, per reference component j
     void* gconst = nullptr;            // [K][32 proj_kblocks] float4 constants per (reference, column)
     int* tile_ref = nullptr;           // [blocks] reference component of every tile of kSelRows rows (regrouped order)
-    int opt_project = 0;               // env GMMVB_PROJECT: "filter" (1) the table filters the carried sweep's proof lists, "only" (2)
-                                       // the sweep itself is stateless (rec_project_kernel); default 0: no table (it does not
-                                       // pay on the benchmark's fits, profiles/r6_experiments.md)
     bool proj_table = false;           // gimg / gconst describe the parameters in force
     bool tile_ref_valid = false;       // tile_ref describes the row order in force
     bool pend_proj = false;            // the pass behind the pending counters used the table (exit_ctr[1]: pairs it left / removed)
@@ -203,20 +173,17 @@ struct gmmvb_workspace {
     void* xp = nullptr;        // [max_rows][D] x in internal row order (storage dtype), allocated with the lists
     int* perm = nullptr, *iperm = nullptr, *perm_tmp = nullptr;   // [npad] each
     bool sorted = false;       // xp / perm / iperm are in force for the matrix xc_src (else the internal order is the caller's)
-    bool sort_rows = true;     // env GMMVB_SORT_ROWS=0: never regroup
     int64_t sorts = 0;         // regroupings since the workspace was created
     double* xc = nullptr;      // [npad][16T] centred f64 copy of the sample matrix (M-step operand), optional
     const void* xc_src = nullptr;   // the x it was made from (null = not prepared)
     int64_t xc_rows = 0, xc_ldx = 0;
     bool xc_stale = false;     // the rows were regrouped since xc was made: it is rebuilt from xp when a kernel needs it
     // c_degree > 128 (generic.h): plain f64 kernels on the raw parameters, no images, no lists
-    bool wide = false;                 // 128 < D <= 256: dense MFMA kernels for 9 .. 16 feature tiles (T rounded up to even)
-    bool generic = false;
     double* gen_u = nullptr;           // [K][D][D]
     double* gen_m = nullptr;           // [K][D]
     double* gen_first = nullptr;       // [gen_S][K][D + 2] partial ns, h, a per row split
     double* gen_second = nullptr;      // [gen_S][K][tri_pairs(T)][256] partial B tiles per row split
-    int gen_S = 1;
+    gmmvb::BufferPlan buffers;         // every device / pinned buffer above, as created (workspace_plan.h); bytes = their sum
     int64_t bytes = 0;
     bool have_params = false;
     int e_state = 0;           // 0 none, 1 E-step output, 2 responsibilities loaded directly, 3 HMM gamma,
@@ -245,14 +212,8 @@ struct gmmvb_workspace {
 };
 
 namespace gmmvb {
-// Environment switches.  Two are part of the interface: GMMVB_ESTEP_PRUNE and GMMVB_MSTEP_SPARSE, read with
-// std::getenv.  Every other GMMVB_* switch is a test / developer seam - it selects between kernels whose results agree, so
-// that a parity test can run each of them - and is only looked at when GMMVB_DEBUG is set ("1"; "2" also prints one line
-// per E-step on stderr).  All of them are read once, when a workspace / HMM state is created.
-inline const char* dev_env(const char* name) {
-    const char* on = std::getenv("GMMVB_DEBUG");
-    return (on && on[0] != '\0' && on[0] != '0') ? std::getenv(name) : nullptr;
-}
+// a developer switch (workspace_plan.h): looked at only when GMMVB_DEBUG is set
+inline const char* dev_env(const char* name) { return dev_switch(std::getenv, name); }
 int fail(int code, const char* what, hipError_t e = hipSuccess);     // sets the thread-local message
 void hmm_state_destroy(gmmvb_hmm_state* h);
 const double* hmm_gamma_cm(const gmmvb_hmm_state* h);                 // [K][npad] responsibilities of the last pass (after hmm_ensure_gamma_cm)
@@ -260,5 +221,4 @@ const double* hmm_gamma_tm(const gmmvb_hmm_state* h);                 // [npad][
 int hmm_padded_states(const gmmvb_hmm_state* h);                      // Kp
 bool hmm_fused_emission(const gmmvb_hmm_state* h);                    // gmmvb_estep hands rho' / mx straight to the HMM state (e_state 4)
 hipError_t hmm_ensure_gamma_cm(gmmvb_hmm_state* h, hipStream_t st);   // transposes gamma once per pass, on demand
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 }  // namespace gmmvb

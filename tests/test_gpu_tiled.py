@@ -191,3 +191,67 @@ def test_tile_group_contract():
     assert torch.equal(b.estep_mstep(xb), sb)
     b.close()
     alone.close()
+
+
+# gmmvb_workspace_bytes as the commit before the buffer plan (bayesml_amd/csrc/workspace_plan.h) reported it, measured once
+# on an MI355X.  That count came from a hand-written formula which, for a workspace with sample lists, had K ints too many
+# for counts / plan / plan_m, an eighth per-block counter that was `apart` again, and not the 32 bytes of exit_ctr: the sum
+# of the plan's sizes differs from it by 32 - 4 K - 8 ceil(npad / 256), and by nothing without lists (profiles/workspace.md).
+_F32, _F64 = torch.float32, torch.float64
+_BYTES = [((1, 8, _F32, 1000), 14176728, False), ((4, 16, _F64, 5000), 58901004, True), ((6, 48, _F32, 5000), 43568636, True),
+          ((8, 64, _F32, 5000), 93205292, True), ((8, 128, _F32, 70000), 307384860, True), ((257, 64, _F32, 2000), 97697472, False),
+          ((4, 160, _F32, 3000), 121298112, False), ((3, 300, _F64, 2000), 3409832, False)]
+_BYTES_GROUP = ((6, 64, _F32, 5000), 71276860, 3000, 2204316)
+_BYTES_ENV = [({"GMMVB_MSTEP_SPARSE": "0"}, 89666464, False), ({"GMMVB_ESTEP_PRUNE": "0"}, 92147052, True),
+              ({"GMMVB_ESTEP_PRUNE": "force"}, 93205292, True), ({"GMMVB_SORT_ROWS": "0"}, 91864620, True),
+              ({"GMMVB_SWEEP_LAZY": "0"}, 93202732, True), ({"GMMVB_MSTEP_CACHE": "0"}, 92229484, True),
+              ({"GMMVB_PROOF": "0"}, 92229484, True), ({"GMMVB_PROJECT": "filter"}, 93242236, True),
+              ({"GMMVB_ESTEP_VARIANT": "i8"}, 93360940, True), ({"GMMVB_POLICY_CALIBRATE": "0"}, 93205292, True)]
+
+
+def test_workspace_bytes():
+    """Creates and destroys workspaces, launches nothing else."""
+    from bayesml_amd._engine import DataPass
+    dev = torch.device("cuda", 0)
+
+    def corrected(parent, K, max_rows, lists):
+        npad = (max_rows + 63) // 64 * 64
+        return parent + (32 - 4 * K - 8 * ((npad + 255) // 256) if lists else 0)
+
+    def created(shape, **kw):
+        eng = DataPass(*shape, dev, **kw)
+        return eng, eng.workspace_bytes
+
+    got, want = [], []
+    for shape, parent, lists in _BYTES:
+        eng, n = created(shape)
+        eng.close()
+        got.append(n)
+        want.append(corrected(parent, shape[0], shape[3], lists))
+    (K, D, dt, n1), parent1, n2, parent2 = _BYTES_GROUP
+    first, b1 = created((K, D, dt, n1))
+    tile, b2 = created((K, D, dt, n2), tile_of=first)
+    first.close()                                      # (the group's buffers go with the tile)
+    tile.close()
+    got += [b1, b2]
+    want += [corrected(parent1, K, n1, True), corrected(parent2, K, n2, True)]
+    names = {k for env, _p, _l in _BYTES_ENV for k in env} | {"GMMVB_DEBUG"}
+    old = {k: os.environ.get(k) for k in names}
+    try:
+        for i, (env, parent, lists) in enumerate(_BYTES_ENV):
+            for k in names:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            if i >= 3:                                 # a developer switch: only looked at under GMMVB_DEBUG
+                os.environ["GMMVB_DEBUG"] = "1"
+            eng, n = created((8, 64, _F32, 5000))
+            eng.close()
+            got.append(n)
+            want.append(corrected(parent, 8, 5000, lists))
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    print(list(zip(got, want)))
+    assert got == want
