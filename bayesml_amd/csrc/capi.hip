@@ -243,6 +243,7 @@ int gmmvb_set_pivot(gmmvb_workspace* ws, const double* pivot_dev, void* stream) 
     ws->xc_src = nullptr;      // the centred copy (if any) is stale now
     ws->xq_src = nullptr;      // ... and so are the digit planes
     ++ws->pivot_gen;
+    ws->quiet_valid = false;
     if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
         ws->lock_live = false;
         ws->lock_reset = true;
@@ -343,6 +344,7 @@ int gmmvb_debug_proof(gmmvb_workspace* ws, int k, int64_t n_rows, float* ub_dev,
     claim_scratch(ws);
     hipStream_t st = (hipStream_t)stream;
     ws->tmeta_valid = false;                                       // (the bound array is written behind the sweeps' back)
+    ws->quiet_valid = false;
     const unsigned grid = (unsigned)((std::max<int64_t>(n_rows, ws->K) + 255) / 256);
     hipLaunchKernelGGL(debug_all_rows_kernel, dim3(grid), dim3(256), 0, st, ws->lists + (int64_t)k * ws->npad, ws->counts, ws->K, k,
                        n_rows);
@@ -372,6 +374,7 @@ int gmmvb_forget(gmmvb_workspace* ws) {
     if (!ws) return fail(GMMVB_EINVAL, "null argument");
     ws->forget = true;
     ws->have_drift = false;
+    ws->quiet_valid = false;
     if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
         ws->lock_live = false;
         ws->lock_reset = true;
@@ -444,6 +447,7 @@ int fetch_counters(gmmvb_workspace* ws) {
             ws->lag.exits = 0.0;
             ws->lag.cols = -1.0;
             ws->lag.left = -1.0;
+            ws->lag_quiet = ws->lag_skipped = -1.0;
             ws->lag.proof = 0.0;
             ws->lag.moved = 0.0;
         } else {
@@ -451,6 +455,8 @@ int fetch_counters(gmmvb_workspace* ws) {
             ws->lag.exits = (ws->exit_host && ws->gather_exit) ? (double)ws->exit_host[0] : 0.0;
             ws->lag.cols = (ws->exit_host && ws->pend_lazy) ? (double)ws->exit_host[1] : -1.0;
             ws->lag.left = (ws->exit_host && ws->pend_proj) ? (double)ws->exit_host[2] : -1.0;
+            ws->lag_quiet = (ws->exit_host && ws->pend_quiet) ? (double)(ws->exit_host[3] & 0xFFFFFFFFull) : -1.0;
+            ws->lag_skipped = (ws->exit_host && ws->pend_quiet) ? (double)(ws->exit_host[3] >> 32) : -1.0;
             ws->lag.settled = ws->ctr_host[4];
             ws->lag.listed = ws->ctr_host[5];
             ws->lag.accum = ws->ctr_host[6];                               // a bound pass / sweep also evaluated every row's (previous) best component
@@ -637,6 +643,7 @@ int gmmvb_prepare_rows(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int6
     if (rc) return rc;
     claim_scratch(ws);                 // (the centred copy is written below)
     ws->bounds_rows = 0;               // (new) sample matrix: nothing of an earlier E-step may be carried over
+    ws->quiet_valid = false;
     if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
         ws->lock_live = false;
         ws->lock_reset = true;

@@ -19,6 +19,7 @@ struct Pass {
     bool i8 = false;
     bool prunable = false;           // a pruned pass may follow this one: a counted dense pass builds its records
     bool prev_lists = false, can_project = false, own_known = false, tmeta_was_valid = false;
+    bool quiet_was_valid = false;    // the tile state of the settled rows described the arrays when the pass began (workspace.h)
     // the plan
     int mode = kPassDense;
     bool settle = false, proof_capable = false;
@@ -26,6 +27,7 @@ struct Pass {
     // the outcome
     bool counted = false, proof_ran = false, tmeta_kept = false, projected = false, filtered = false, emission_to_hmm = false,
          sorted_now = false;
+    bool quiet_swept = false;        // the sweep counted the tiles' loose rows (tile_loose is this pass's)
     bool phase_closed = false;       // the pass recorded the end of the profile's E phase itself
     const char* name = "";           // the info line (nullptr: the pass wrote its own)
     int rpw = 0;
@@ -372,6 +374,10 @@ int Pass::sweep_bounds(bool proof, bool own_round) {
     unsigned char* lock = settle ? ws->lock : nullptr;
     unsigned long long* pmask = proof ? ws->rmask : nullptr;
     const int proof_all = ws->opt_proof_all ? 1 : 0, own_fresh = own_round ? 1 : 0;
+    // the tile state (workspace.h) is kept by the carried forms only, and not next to the table's filter
+    int* tile_loose = can_project ? nullptr : ws->tile_loose();
+    unsigned long long* quiet_ctr = (tile_loose && ws->opt_debug) ? ws->exit_ctr + 3 : nullptr;
+    if (quiet_ctr) note_hip(ws, hipMemsetAsync(quiet_ctr, 0, sizeof(unsigned long long), st));
     if (can_project && ws->opt_project == 2) {
         // bounds from the table of the parameters in force and the rows' digit planes: nothing carried, nothing
         // written back (the per-pair array is void afterwards: ws->dense_valid in finish())
@@ -388,13 +394,16 @@ int Pass::sweep_bounds(bool proof, bool own_round) {
             hipLaunchKernelGGL((rec_sweep_kernel<true, true, decltype(wc)::value>), dim3(sel_grid), dim3(kSelRows), 0, st, ws->ub32,
                                ws->lnrho, ws->npad, n_rows, ws->K, ws->drift, ws->cvec, ws->khat, rec, ws->masks, ws->blk,
                                ws->epart, ws->opart, lock, ws->dlock, ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all, own_fresh,
-                               ws->tmeta, tmeta_was_valid ? 0 : 1, ws->exit_ctr + 1, ws->ppart);
+                               ws->tmeta, tmeta_was_valid ? 0 : 1, ws->exit_ctr + 1, ws->ppart, tile_loose, quiet_ctr);
         });
         tmeta_kept = true;
+        quiet_swept = tile_loose != nullptr;
     } else {
         hipLaunchKernelGGL(rec_sweep_kernel<true>, dim3(sel_grid), dim3(kSelRows), 0, st, ws->ub32, ws->lnrho, ws->npad, n_rows,
                            ws->K, ws->drift, ws->cvec, ws->khat, rec, ws->masks, ws->blk, ws->epart, ws->opart, lock, ws->dlock,
-                           ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all, own_fresh, nullptr, 0, nullptr, ws->ppart);
+                           ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all, own_fresh, nullptr, 0, nullptr, ws->ppart, tile_loose,
+                           quiet_ctr);
+        quiet_swept = tile_loose != nullptr;
     }
     return GMMVB_OK;
 }
@@ -423,7 +432,7 @@ int Pass::run_sweep_over_lists() {
     if (own_round) {
         span_begin(ws, kSpanSelect, st);
         hipLaunchKernelGGL(settled_mask_kernel, dim3(sel_grid), dim3(kSelRows), 0, st, ws->lock, ws->masks, ws->lcomp, ws->npad,
-                           n_rows, ws->K, ws->rmask, ws->rblk, ws->drift, ws->spart);
+                           n_rows, ws->K, ws->rmask, ws->rblk, ws->drift, ws->spart, quiet_was_valid ? ws->tile_quiet() : nullptr);
         scan_and_fill(ws, st, ws->rmask, ws->rblk, sel_grid, n_rows, ws->K, ws->spart);
         span_end(ws, st);
         span_begin(ws, kSpanProof, st);
@@ -456,7 +465,7 @@ int Pass::run_sweep_over_lists() {
         span_begin(ws, kSpanSelect, st);
         hipLaunchKernelGGL(rec_proof_decide_kernel, dim3(sel_grid), dim3(kSelRows), 0, st, rec, ws->rmask, ws->masks, ws->npad,
                            n_rows, ws->K, ws->cvec, ws->ub32, ws->lnrho, ws->lcomp, ws->dlock, ws->rthr, ws->blk, ws->epart,
-                           ws->ppart, own_round ? ws->spart : nullptr);
+                           ws->ppart, own_round ? ws->spart : nullptr, quiet_swept ? ws->tile_loose() : nullptr);
         proof_ran = true;
     }
     span_end(ws, st);
@@ -504,7 +513,9 @@ int Pass::run_candidates() {
     hipLaunchKernelGGL(rec_finish_kernel, dim3(sel_grid), dim3(kSelRows), 0, st, rec, ws->lnrho, ws->npad, n_rows, ws->K,
                        ws->cvec, ws->lse, ws->khat, ws->masks, ws->blk, ws->apart, ws->mpart, ws->ub32,
                        settle ? ws->lock : nullptr, ws->dlock, skip_margin, settle ? ws->dmask : nullptr,
-                       settle ? ws->dblk : nullptr, ws->mmask, ws->mblk, ws->spart, ws->gpart, ws->qpart, ws->rthr, ws->lcomp);
+                       settle ? ws->dblk : nullptr, ws->mmask, ws->mblk, ws->spart, ws->gpart, ws->qpart, ws->rthr, ws->lcomp,
+                       quiet_swept ? ws->tile_loose() : nullptr, quiet_swept ? ws->tile_quiet() : nullptr, quiet_was_valid ? 1 : 0,
+                       (quiet_swept && ws->opt_debug) ? ws->exit_ctr + 3 : nullptr);
     if (!proof_ran) note_hip(ws, hipMemsetAsync(ws->ctr + 7, 0, sizeof(double), st));
     hipLaunchKernelGGL(sum_parts_kernel, dim3(proof_ran ? 8 : 7), dim3(1024), 0, st, ws->apart, ws->epart, ws->opart, ws->mpart,
                        ws->spart, ws->gpart, ws->qpart, ws->ppart, sel_grid, ws->ctr);
@@ -515,6 +526,7 @@ int Pass::run_candidates() {
     ws->rec_valid = true;
     ws->rec_live = true;
     ws->evaluated = -1.0;
+    ws->quiet_valid = quiet_swept;     // (rec_finish_kernel has just written tile_quiet for every tile)
     if (settle) {
         ws->lock_live = true;
         ws->delta_pending = true;
@@ -531,6 +543,7 @@ int Pass::finish(const char* latch_what) {
     ws->tmeta_valid = tmeta_kept;
     ws->pend_lazy = tmeta_kept;
     ws->pend_proj = projected || filtered;
+    ws->pend_quiet = quiet_swept && ws->opt_debug;
     // the E phase of the profile ends behind the pass's LAST kernel (round 4; before, rec_finish / lse_mask - 0.2-0.4 ms of
     // E-step work at the benchmark shape - fell between the two phases and were booked as "outside the data pass")
     if (!phase_closed && phase_events(ws)) {
@@ -541,7 +554,7 @@ int Pass::finish(const char* latch_what) {
     if (counted) {
         hipError_t e = hipMemcpyAsync(ws->ctr_host, ws->ctr, 8 * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && ws->exit_ctr && mode != kPassDense)
-            e = hipMemcpyAsync(ws->exit_host, ws->exit_ctr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(ws->exit_host, ws->exit_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipEventRecord(ws->ctr_ev, st);
         if (e != hipSuccess) return fail(GMMVB_EHIP, "E-step counters", e);
         ws->ctr_pending = true;
@@ -650,6 +663,7 @@ int Pass::apply(const PassFacts& f, const PassPlan& plan) {
             if (e != hipSuccess) return fail(GMMVB_EHIP, "resetting the cache of single-component rows", e);
             ws->lock_live = false;
             ws->skip_used = false;
+            ws->quiet_valid = false;
         }
         ws->lock_reset = false;
         ws->delta_pending = false;
@@ -662,9 +676,13 @@ int Pass::apply(const PassFacts& f, const PassPlan& plan) {
     if (ws->opt_debug) {
         const gmmvb_pass_counters& L = f.L;
         const double rows_l = f.rows_l();
-        std::fprintf(stderr, "[gmmvb] estep: mode=%d known=%d lag(mode=%d act=%.3g eval=%.3g over=%.3g settled=%.3g listed=%.3g) gamma=%.3f rec_valid=%d drift=%d settle=%d\n",
+        // (quiet: tiles the lag pass's sweep left without a loose row, of its tiles; skipped: tiles rec_finish_kernel did not
+        // go through row by row - quiet there too, after the proof round, and in the pass before; -1: no tile state kept)
+        std::fprintf(stderr, "[gmmvb] estep: mode=%d known=%d lag(mode=%d act=%.3g eval=%.3g over=%.3g settled=%.3g listed=%.3g) gamma=%.3f rec_valid=%d drift=%d settle=%d quiet=%.0f/%lld skipped=%.0f\n",
                      plan.mode, (int)f.known, L.mode, L.act / rows_l, L.eval / rows_l, L.over / rows_l, L.settled / rows_l,
-                     L.listed / rows_l, ws->typical_gamma, (int)ws->rec_valid, (int)ws->have_drift, (int)plan.settle);
+                     L.listed / rows_l, ws->typical_gamma, (int)ws->rec_valid, (int)ws->have_drift, (int)plan.settle,
+                     ws->lag.valid ? ws->lag_quiet : -1.0, (long long)((n_rows + kSelRows - 1) / kSelRows),
+                     ws->lag.valid ? ws->lag_skipped : -1.0);
     }
     // (the caller hands over drift hints - a row-tiled pass, whose bounds do not survive the other tiles, does not)
     const bool wants_drift = gmmvb_wants_drift(ws, n_rows) != 0;
@@ -728,6 +746,8 @@ int gmmvb_estep(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int64_t n_r
     ws->lse_stale = false;
     p.tmeta_was_valid = ws->tmeta_valid;
     ws->tmeta_valid = false;            // (only a lazy sweep that ran to its end leaves the tile state in step with the bounds)
+    p.quiet_was_valid = ws->quiet_valid && !plan.regroup && ws->tile_quiet() != nullptr;
+    ws->quiet_valid = false;            // (only a counted sweep that ran to its end leaves the settled rows' tile state valid)
     if (p.mode == kPassDense) {
         rc = p.run_dense();
     } else {

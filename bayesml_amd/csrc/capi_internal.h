@@ -106,6 +106,7 @@ static inline ProjectArgs project_args(const gmmvb_workspace* ws, int64_t n_rows
 // carries into its next E-step (bounds, records, settled rows, digit planes, row order, policy counters) is untouched; that
 // E-step starts its first round from the rows' best components instead of the previous pass's lists.
 static inline void yield_scratch(gmmvb_workspace* w) {
+    w->quiet_valid = false;
     // its counters, masks and block counts (per tile) still describe that pass: gmmvb_last_sparsity / gmmvb_last_work answer,
     // and the next sweep rebuilds its first round's lists from them (blk_fresh stays as it is)
     w->lost_estep = w->e_state == 1;

@@ -17,6 +17,7 @@ int gmmvb_load_responsibilities(gmmvb_workspace* ws, const double* r_dev, int64_
     ws->e_rows = n_rows;
     ws->n_spans = 0;
     ws->bounds_rows = 0;               // the array holds responsibilities now, nothing a later E-step may carry over
+    ws->quiet_valid = false;
     if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
         ws->lock_live = false;
         ws->lock_reset = true;

@@ -35,6 +35,7 @@ static int refresh_settled(gmmvb_workspace* ws, hipStream_t st) {
     if (ws->mlists_done) ws->mlists_lost = true;
     ws->mlists_done = false;
     ws->settled_fresh = true;
+    // (the settled rows' tile state - workspace.h, quiet_valid - stands: none of the arrays it speaks of was written here)
     return GMMVB_OK;
 }
 

@@ -356,7 +356,11 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
                                                              int tmeta_reset = 0 /*LAZY: the stored tile state is void*/,
                                                              unsigned long long* __restrict__ col_ctr = nullptr /*LAZY: += columns opened*/,
                                                              double* __restrict__ ppre = nullptr /*[blocks] pairs listed for the proof
-                                                                 round (fill_lists_kernel skips the blocks without any)*/) {
+                                                                 round (fill_lists_kernel skips the blocks without any)*/,
+                                                             int* __restrict__ tile_loose = nullptr /*[blocks] valid rows the sweep
+                                                                 does not leave flagged 4 (workspace.h: tile state)*/,
+                                                             unsigned long long* __restrict__ quiet_ctr = nullptr /*+= tiles without
+                                                                 one (GMMVB_DEBUG=2)*/) {
     static_assert(!LAZY || PREV, "the lazy sweep is a form of the PREV sweep");
     __shared__ int wcnt[4][256];
     __shared__ int pcnt[4][256];
@@ -365,7 +369,7 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
     __shared__ double sc[256];
     __shared__ unsigned char sfirst[256];
     __shared__ float s_delta[256];      // this pass's delta, rounded up
-    __shared__ int wsum[3][4];
+    __shared__ int wsum[4][4];
     __shared__ unsigned char s_force[LAZY ? 256 : 1];      // a row of the tile holds an exact value in this column
     __shared__ float s_thr[LAZY ? 4 : 1];                  // per wave: lowest threshold of its rows
     __shared__ unsigned long long s_open[LAZY ? 4 : 1];    // columns the tile's rows go through
@@ -756,6 +760,8 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
         if (pmask) count_word(pm[w], w, wave, pcnt);
         plisted += __builtin_popcountll(pm[w]);
     }
+    // (rows that are not left settled: a ballot, not a fourth butterfly)
+    const int loose_w = __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && !stays));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         listed += __shfl_xor(listed, o);
@@ -766,6 +772,7 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
         wsum[0][wave] = listed;
         wsum[1][wave] = over_i;
         wsum[2][wave] = plisted;
+        wsum[3][wave] = loose_w;
     }
     if constexpr (LAZY) {
         if (lane == 0)
@@ -809,6 +816,11 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
         epart[blockIdx.x] = (double)(wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3]);
         opart[blockIdx.x] = (double)(wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3]);
         if (ppre) ppre[blockIdx.x] = (double)(wsum[2][0] + wsum[2][1] + wsum[2][2] + wsum[2][3]);
+        if (tile_loose) {
+            const int loose = wsum[3][0] + wsum[3][1] + wsum[3][2] + wsum[3][3];
+            tile_loose[blockIdx.x] = loose;
+            if (quiet_ctr && loose == 0) atomicAdd(quiet_ctr, 1ull);
+        }
     }
 }
 
@@ -829,9 +841,10 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
                                                                     int* __restrict__ blk_cnt, double* __restrict__ epart,
                                                                     double* __restrict__ ppart,
                                                                     const double* __restrict__ own_part /*[blocks] pairs of the
-                                                                        round before the sweep (own_first), or null*/) {
+                                                                        round before the sweep (own_first), or null*/,
+                                                                    int* __restrict__ tile_loose = nullptr /*[blocks] -= rows back to flag 4*/) {
     __shared__ int wcnt[4][256];
-    __shared__ int wsum[2][4];
+    __shared__ int wsum[3][4];
     const int tid = threadIdx.x, wave = tid >> 6;
     const int W = (K + 63) / 64;
     for (int k = tid & 63; k < K; k += 64) wcnt[wave][k] = 0;
@@ -842,6 +855,7 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
     // (64 bytes per row at K = 256 for rows that have nothing to decide: 0.5-0.9 ms per pass at config 4)
     unsigned long long mk[4] = {0ull, 0ull, 0ull, 0ull}, old[4] = {0ull, 0ull, 0ull, 0ull};
     int listed = 0, proved = 0;
+    bool back = false;                                          // the row returns to flag 4
     const unsigned fl0 = valid ? rec.flags[n] : 0u;
     if (valid && ((fl0 & 16u) || fl0 == 8u)) {
         for (int w = 0; w < W; ++w) old[w] = mk[w] = masks[(int64_t)w * npad + n];
@@ -942,6 +956,7 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
             }
             if (!any && l > -__builtin_huge_val()) {
                 rec.flags[n] = 4;
+                back = true;
                 dlock[n] = f32_up(dist_of(cvec[kset], l) * (1.0 + 1e-9));
             } else {
                 kept[kset >> 6] |= 1ull << (kset & 63);
@@ -975,6 +990,7 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
         }
     }
     for (int w = 0; w < W; ++w) count_word(mk[w], w, wave, wcnt);
+    const int back_w = __builtin_popcountll(__builtin_amdgcn_ballot_w64(back));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         listed += __shfl_xor(listed, o);
@@ -983,6 +999,7 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
     if ((tid & 63) == 0) {
         wsum[0][wave] = listed;
         wsum[1][wave] = proved;
+        wsum[2][wave] = back_w;
     }
     __syncthreads();
     const int joined = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
@@ -994,6 +1011,8 @@ static __global__ __launch_bounds__(kSelRows) void rec_proof_decide_kernel(RecAr
     if (tid == 0) {
         if (joined != 0) epart[blockIdx.x] += (double)joined;
         ppart[blockIdx.x] = (double)(wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3]) + (own_part ? own_part[blockIdx.x] : 0.0);
+        const int returned = wsum[2][0] + wsum[2][1] + wsum[2][2] + wsum[2][3];
+        if (tile_loose && returned != 0) tile_loose[blockIdx.x] -= returned;
     }
 }
 
@@ -1132,12 +1151,37 @@ static __global__ __launch_bounds__(kSelRows) void rec_finish_kernel(RecArrays r
                                                               double* __restrict__ spart, double* __restrict__ gpart,
                                                               double* __restrict__ qpart /*pairs the M-step accumulates*/,
                                                               const float* __restrict__ rthr /*[npad] relevance thresholds*/,
-                                                              unsigned char* __restrict__ lcomp /*[npad] component a cached row is in*/) {
+                                                              unsigned char* __restrict__ lcomp /*[npad] component a cached row is in*/,
+                                                              const int* __restrict__ tile_loose = nullptr /*[blocks] valid rows not
+                                                                  flagged 4, as the sweep and the proof round of this pass left it*/,
+                                                              int* __restrict__ tile_quiet = nullptr /*[blocks] (workspace.h: tile state)*/,
+                                                              int quiet_valid = 0 /*tile_quiet still describes the arrays*/,
+                                                              unsigned long long* __restrict__ quiet_ctr = nullptr /*upper half +=
+                                                                  tiles that took the way out below (GMMVB_DEBUG=2)*/) {
     __shared__ int wcnt[4][256];
     __shared__ int dcnt[4][256];
     __shared__ int mcnt[4][256];
     __shared__ int wact[4], wmov[4], wset[4], wlist[4], wacc[4];
     const int tid = threadIdx.x, wave = tid >> 6;
+    // A tile whose valid rows were all flagged 4 when this kernel last went over it, and are again: every row below would take
+    // the first branch (one active pair, settled, nothing written) and store the zero mask words that are there already -
+    // masks by this pass's sweep, dmask / mmask by that earlier visit.  What is left are the per-block outputs, all constants
+    // (the scans turned the last pass's zero counts into bases in place: they are written again).
+    const int loose = tile_loose ? tile_loose[blockIdx.x] : -1;
+    if (quiet_valid && loose == 0 && tile_quiet[blockIdx.x] == 1) {
+        for (int k = tid; k < K; k += kSelRows) {
+            blk_cnt[blk_at(k, blockIdx.x, K)] = 0;
+            if (dblk) dblk[blk_at(k, blockIdx.x, K)] = mblk[blk_at(k, blockIdx.x, K)] = 0;
+        }
+        if (tid == 0) {
+            const int64_t left = n_rows - (int64_t)blockIdx.x * kSelRows;
+            const double rows = (double)(left < kSelRows ? left : (int64_t)kSelRows);
+            apart[blockIdx.x] = spart[blockIdx.x] = rows;
+            mpart[blockIdx.x] = gpart[blockIdx.x] = qpart[blockIdx.x] = 0.0;
+            if (quiet_ctr) atomicAdd(quiet_ctr, 1ull << 32);
+        }
+        return;
+    }
     const int W = (K + 63) / 64;
     for (int k = tid & 63; k < K; k += 64) wcnt[wave][k] = dcnt[wave][k] = mcnt[wave][k] = 0;
     const int64_t n = (int64_t)blockIdx.x * kSelRows + tid;
@@ -1450,6 +1494,7 @@ static __global__ __launch_bounds__(kSelRows) void rec_finish_kernel(RecArrays r
         spart[blockIdx.x] = (double)(wset[0] + wset[1] + wset[2] + wset[3]);
         gpart[blockIdx.x] = (double)(wlist[0] + wlist[1] + wlist[2] + wlist[3]);
         qpart[blockIdx.x] = (double)(wacc[0] + wacc[1] + wacc[2] + wacc[3]);
+        if (tile_quiet) tile_quiet[blockIdx.x] = loose == 0 ? 1 : 0;
     }
 }
 
@@ -1499,7 +1544,9 @@ static __global__ __launch_bounds__(kSelRows) void settled_mask_kernel(const uns
                                                                 int* __restrict__ blk_cnt,
                                                                 const double* __restrict__ drift = nullptr /*only the rows of
                                                                     own_first components (the sweep's first proof round)*/,
-                                                                double* __restrict__ listed_part = nullptr /*[blocks] rows listed*/) {
+                                                                double* __restrict__ listed_part = nullptr /*[blocks] rows listed*/,
+                                                                const int* __restrict__ tile_quiet = nullptr /*[blocks], while it
+                                                                    describes the arrays (workspace.h: tile state)*/) {
     __shared__ int wcnt[4][256];
     const int64_t n = (int64_t)blockIdx.x * kSelRows + threadIdx.x;
     const bool valid = n < n_rows;
@@ -1508,10 +1555,14 @@ static __global__ __launch_bounds__(kSelRows) void settled_mask_kernel(const uns
     for (int k = threadIdx.x & 63; k < K; k += 64) wcnt[wave][k] = 0;
     // (the three per-row loads at once: lock -> mask -> component in turn was three memory round trips per workgroup)
     const int64_t nn = valid ? n : 0;
-    const unsigned lk = lock[nn];
     const int lc = (int)lcomp[nn];
+    unsigned lk = 1u;
     unsigned long long any = 0ull;
-    for (int w = 0; w < W; ++w) any |= emask[(int64_t)w * npad + nn];
+    // (a quiet tile: every valid row is in the cache and in none of the E-step's lists - only its component is read)
+    if (!(tile_quiet && tile_quiet[blockIdx.x] == 1)) {
+        lk = lock[nn];
+        for (int w = 0; w < W; ++w) any |= emask[(int64_t)w * npad + nn];
+    }
     int kh = (valid && lk == 1u && any == 0ull) ? lc : -1;          // in the cache and in none of the E-step's lists
     if (kh >= 0 && drift != nullptr && !own_first(drift[3 * K + kh], drift[K + kh])) kh = -1;
     for (int w = 0; w < W; ++w) {

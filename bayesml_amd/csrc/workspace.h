@@ -130,7 +130,9 @@ struct gmmvb_workspace : gmmvb::WorkspaceShape {
     float* rthr = nullptr;             // [npad] relevance threshold of the selection round (best exact value - 80 ln 2)
     unsigned long long* exit_ctr = nullptr;    // [4] device: candidate pairs of the pass that took the gather's early way out;
                                                //     (tile, component) columns the lazy sweep opened; pairs the table of
-                                               //     project.h took off the proof lists (stateless sweep: pairs it left)
+                                               //     project.h took off the proof lists (stateless sweep: pairs it left);
+                                               //     tiles the sweep left without a loose row | tiles rec_finish_kernel
+                                               //     skipped << 32 (GMMVB_DEBUG=2 only)
     unsigned long long* exit_host = nullptr;   // [4] pinned mirror (copied with the other counters)
     bool pend_lazy = false;                    // the pass behind the pending counters was a lazy sweep
     unsigned long long* dmask = nullptr;   // [ceil(K / 64)][npad] rows entering / leaving the cache in this pass
@@ -168,6 +170,27 @@ struct gmmvb_workspace : gmmvb::WorkspaceShape {
     bool pend_proj = false;            // the pass behind the pending counters used the table (exit_ctr[1]: pairs it left / removed)
     float4* tmeta = nullptr;           // [blocks][K] the lazy sweep's state per tile and component (records.h)
     bool tmeta_valid = false;          // it describes the bound array as it is (only sweeps have written to it since)
+    // Tile state of the settled rows (records.h), two ints per selection block of kSelRows rows:
+    //   tile_loose[b]  valid rows of the tile whose flag is not 4 in the pass in flight: written by the PREV forms of
+    //                  rec_sweep_kernel, lowered by rec_proof_decide_kernel by the rows it returns to flag 4;
+    //   tile_quiet[b]  1 if tile_loose[b] was 0 when rec_finish_kernel last went over the tile.
+    // While quiet_valid holds, a tile with tile_quiet == 1 is as that visit left it: every valid row has lock == 1; its rows
+    // of masks, mmask and dmask are zero; khat, lcomp and lse are not due a write.  On these rest the shortcuts of
+    // rec_finish_kernel (a tile quiet then and now: the per-block constants only) and settled_mask_kernel (own round: lcomp
+    // only).  Set at the end of run_candidates of a sweep that counted (not the projected / filtered form); cleared - like
+    // tmeta_valid: when in doubt - by every E-step before its first launch (so by dense and bound passes and the
+    // regrouping), by a cache reset, and by whatever else touches those arrays or the row order: load_r, yield_scratch, a
+    // new matrix or pivot, gmmvb_forget, the diagnostic proof.  (The read-out of settled rows writes lse, ln rho entries
+    // and the read-out lists only: the state stands.)
+    // The two arrays live in perm_tmp, which is idle between regroupings (a regrouping voids the state anyway): the
+    // workspace's buffer list and its byte count stay what they were.  A workspace that shares its scratch with other tiles
+    // loses it to them before every pass of its own - the state would never be valid - and keeps none.
+    bool quiet_valid = false;
+    bool pend_quiet = false;           // the pass behind the pending counters counted its quiet tiles (exit_ctr[3])
+    double lag_quiet = -1.0;           // ... and their number once the copy has arrived (< 0: not counted; GMMVB_DEBUG=2)
+    double lag_skipped = -1.0;         // ... and the tiles rec_finish_kernel took the short way through (the counter's upper half)
+    int* tile_loose() const { return (opt_quiet_tiles && perm_tmp && !(scratch && scratch->refs > 1)) ? perm_tmp : nullptr; }
+    int* tile_quiet() const { return tile_loose() ? perm_tmp + (npad + 255) / 256 : nullptr; }
     double* ppart = nullptr;           // [blocks] pairs of the proof round per selection block
     // rows grouped by dominant component (aux_kernels.h): internal row i = the caller's row perm[i]
     void* xp = nullptr;        // [max_rows][D] x in internal row order (storage dtype), allocated with the lists

@@ -52,6 +52,7 @@ struct WorkspaceOptions {
     bool opt_carry_off = false;        // GMMVB_ESTEP_CARRY_OFF (set at all): ignore gmmvb_set_drift
     bool opt_hmm_mstep_dense = false;  // GMMVB_HMM_MSTEP_DENSE (set at all): the HMM's small M-step walks every (step, state)
     bool opt_calibrate = true;         // GMMVB_POLICY_CALIBRATE=0: the scaled literals only
+    bool opt_quiet_tiles = true;       // GMMVB_QUIET_TILES=0: no tile-level shortcuts for tiles of settled rows (workspace.h)
     bool opt_debug = false;            // GMMVB_DEBUG=2
 
     // lookup: const char* (const char* name), null for an unset name - std::getenv in the library
@@ -77,6 +78,7 @@ struct WorkspaceOptions {
         o.opt_carry_off = dev("GMMVB_ESTEP_CARRY_OFF") != nullptr;
         o.opt_hmm_mstep_dense = dev("GMMVB_HMM_MSTEP_DENSE") != nullptr;
         o.opt_calibrate = not_zero(dev("GMMVB_POLICY_CALIBRATE"));
+        o.opt_quiet_tiles = not_zero(dev("GMMVB_QUIET_TILES"));
         o.opt_debug = lookup("GMMVB_DEBUG") && lookup("GMMVB_DEBUG")[0] == '2';
         return o;
     }
