@@ -243,11 +243,7 @@ int gmmvb_set_pivot(gmmvb_workspace* ws, const double* pivot_dev, void* stream) 
     ws->xc_src = nullptr;      // the centred copy (if any) is stale now
     ws->xq_src = nullptr;      // ... and so are the digit planes
     ++ws->pivot_gen;
-    ws->quiet_valid = false;
-    if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
-        ws->lock_live = false;
-        ws->lock_reset = true;
-    }
+    drop_settled_rows(ws);
     return GMMVB_OK;
 }
 
@@ -344,7 +340,7 @@ int gmmvb_debug_proof(gmmvb_workspace* ws, int k, int64_t n_rows, float* ub_dev,
     claim_scratch(ws);
     hipStream_t st = (hipStream_t)stream;
     ws->tmeta_valid = false;                                       // (the bound array is written behind the sweeps' back)
-    ws->quiet_valid = false;
+    drop_settled_rows(ws);
     const unsigned grid = (unsigned)((std::max<int64_t>(n_rows, ws->K) + 255) / 256);
     hipLaunchKernelGGL(debug_all_rows_kernel, dim3(grid), dim3(256), 0, st, ws->lists + (int64_t)k * ws->npad, ws->counts, ws->K, k,
                        n_rows);
@@ -363,10 +359,6 @@ int gmmvb_debug_proof(gmmvb_workspace* ws, int k, int64_t n_rows, float* ub_dev,
     ws->rec_valid = ws->dense_valid = ws->rec_live = false;
     ws->active_lists = ws->blk_fresh = false;
     ws->lag.valid = false;
-    if (ws->lock_live) {
-        ws->lock_live = false;
-        ws->lock_reset = true;
-    }
     return GMMVB_OK;
 }
 
@@ -374,11 +366,7 @@ int gmmvb_forget(gmmvb_workspace* ws) {
     if (!ws) return fail(GMMVB_EINVAL, "null argument");
     ws->forget = true;
     ws->have_drift = false;
-    ws->quiet_valid = false;
-    if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
-        ws->lock_live = false;
-        ws->lock_reset = true;
-    }
+    drop_settled_rows(ws);
     return GMMVB_OK;
 }
 
@@ -643,11 +631,7 @@ int gmmvb_prepare_rows(gmmvb_workspace* ws, const void* x_dev, int64_t ldx, int6
     if (rc) return rc;
     claim_scratch(ws);                 // (the centred copy is written below)
     ws->bounds_rows = 0;               // (new) sample matrix: nothing of an earlier E-step may be carried over
-    ws->quiet_valid = false;
-    if (ws->lock_live) {               // the settled rows belonged to the previous state of affairs
-        ws->lock_live = false;
-        ws->lock_reset = true;
-    }
+    drop_settled_rows(ws);
     ws->sorted = false;                // ... and the internal row order is the caller's again
     ws->tile_ref_valid = false;
     ws->rec_valid = false;

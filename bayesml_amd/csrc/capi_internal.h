@@ -73,6 +73,15 @@ static inline void span_end(gmmvb_workspace* ws, hipStream_t st) {
     ++ws->n_spans;
 }
 static inline bool phase_events(const gmmvb_workspace* ws) { return ws->prof && !ws->prof_light; }
+// The settled rows belonged to the previous state of affairs (other responsibilities, matrix, pivot or parameters): their
+// tile state is void and the next E-step empties the cache.
+static inline void drop_settled_rows(gmmvb_workspace* ws) {
+    ws->quiet_valid = false;
+    if (ws->lock_live) {
+        ws->lock_live = false;
+        ws->lock_reset = true;
+    }
+}
 
 // ---- expressions and launch groups the passes share ---------------------------------------------------------------------
 // the centred copy (gmmvb_prepare_rows) is of this matrix / the digit planes exist and are of this matrix

@@ -43,7 +43,7 @@ def kernel_sizes(K, D):
 # ---- the parent's create_workspace, line by line ---------------------------------------------------------------------------
 DEFAULTS = dict(sparse=1, prune=1, variant_asked=-1, sort_rows=1, settle_margin=1e300, opt_proof=1, opt_proof_all=1,
                 opt_proof_blocked=1, opt_lazy=1, opt_project=0, opt_regroup_margin=1, gather_exit=1, cache_on=1, opt_carry_off=0,
-                opt_hmm_mstep_dense=0, opt_calibrate=1, opt_debug=0)
+                opt_hmm_mstep_dense=0, opt_calibrate=1, opt_debug=0, opt_mlist_xc=0)
 LDS, DIRECT, LDS8, I8, VALU16 = 0, 1, 2, 3, 4
 
 
@@ -71,6 +71,8 @@ def parent_options(env):
     o["opt_hmm_mstep_dense"] = int(dev("GMMVB_HMM_MSTEP_DENSE") is not None)
     o["opt_calibrate"] = not_zero(dev("GMMVB_POLICY_CALIBRATE"))
     o["opt_debug"] = int(dbg is not None and dbg[:1] == "2")
+    # (gmmvb_mstep read this one, at its first list pass: dev_env(..) && dev_env(..)[0] == '1')
+    o["opt_mlist_xc"] = int(dev("GMMVB_MLIST_XC") is not None and dev("GMMVB_MLIST_XC")[:1] == "1")
     return o
 
 
@@ -208,6 +210,8 @@ OPTIONS += [(dict(DBG, GMMVB_PROJECT=v), {"opt_project": p}) for v, p in (("0", 
 OPTIONS += [(dict(DBG, GMMVB_ESTEP_VARIANT=v), {"variant_asked": e})
             for v, e in (("0", -1), ("1", -1), ("lds8", LDS8), ("direct", DIRECT), ("lds4", LDS), ("i8", I8), ("only", -1))]
 OPTIONS += [(dict(DBG, GMMVB_SETTLE_MARGIN=v), {"settle_margin": m}) for v, m in (("2.5", 2.5), ("-1", -1.0), ("0", 0.0))]
+OPTIONS += [(dict(DBG, GMMVB_MLIST_XC=v), {"opt_mlist_xc": on}) for v, on in (("1", 1), ("0", 0), ("", 0), ("force", 0))]
+OPTIONS += [({"GMMVB_MLIST_XC": "1"}, {})]
 # a developer switch is ignored without GMMVB_DEBUG (unset, "0", empty); the two interface switches are not
 for dbg in ({}, {"GMMVB_DEBUG": "0"}, {"GMMVB_DEBUG": ""}):
     OPTIONS += [(dict(dbg, **{name: "0"}), {}) for name in DEV_SWITCHES]

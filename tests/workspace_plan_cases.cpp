@@ -70,10 +70,10 @@ struct Case {
 void print_options(const WorkspaceOptions& o) {
     std::printf("sparse=%d prune=%d variant_asked=%d sort_rows=%d settle_margin=%.17g opt_proof=%d opt_proof_all=%d opt_proof_blocked=%d "
                 "opt_lazy=%d opt_project=%d opt_regroup_margin=%d gather_exit=%d cache_on=%d opt_carry_off=%d opt_hmm_mstep_dense=%d "
-                "opt_calibrate=%d opt_debug=%d", (int)o.sparse, o.prune, o.variant_asked, (int)o.sort_rows, o.settle_margin,
+                "opt_calibrate=%d opt_debug=%d opt_mlist_xc=%d", (int)o.sparse, o.prune, o.variant_asked, (int)o.sort_rows, o.settle_margin,
                 (int)o.opt_proof, (int)o.opt_proof_all, (int)o.opt_proof_blocked, (int)o.opt_lazy, o.opt_project,
                 (int)o.opt_regroup_margin, (int)o.gather_exit, (int)o.cache_on, (int)o.opt_carry_off, (int)o.opt_hmm_mstep_dense,
-                (int)o.opt_calibrate, (int)o.opt_debug);
+                (int)o.opt_calibrate, (int)o.opt_debug, (int)o.opt_mlist_xc);
 }
 
 // ---- a workspace over malloc ---------------------------------------------------------------------------------------------
