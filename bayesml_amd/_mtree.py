@@ -4,6 +4,8 @@ The division of labour is ``_ctree``'s: PyTorch owns device memory and the strea
 segmented reduction of y, the bottom-up sweep and the predictive fold are gfx950 kernels of ``csrc/mtree_kernels.h``; what
 touches one node tree (materialising ``_Node`` objects, the MAP tree, feature importances) is host code in
 ``bayesml_amd.metatree``.  No CPU fallback: without the library or a GPU, ``MtreePass`` raises ``EngineUnavailableError``.
+The linear-regression family (``LINREG``, kernels in ``csrc/mtree_lr_kernels.h``) reduces x as well: ``reduce_x`` hands the
+feature matrix to ``mtree_reduce_x``, and the predictive table is sized by ``mtree_values_len``.
 
 The forest lives in flat tables over all trees (``FlatForest``): ``tree_off[B + 1]``, and per node ``feat`` (-1 for a leaf),
 ``child0``, ``nchild``, ``thr_off``, ``depth``, nodes of a tree in breadth-first order; the state is ``g[nodes]``,
@@ -23,10 +25,11 @@ from ._native import PLOT_MSG, bind, gpu_device, stream_ptr  # noqa: F401  (PLOT
 from ._expfam import adopt_tensor
 
 U8, I32, I64, F32, F64 = range(5)                                  # enum mtree_dtype
-BERNOULLI, CATEGORICAL, POISSON, EXPONENTIAL, NORMAL = range(5)    # enum mtree_family
+BERNOULLI, CATEGORICAL, POISSON, EXPONENTIAL, NORMAL, LINREG = range(6)    # enum mtree_family
 PRED_MEAN, PRED_PROBA, PRED_CLASS, PRED_VAR = range(4)             # enum mtree_pred
 MAX_TREES, MAX_NODES, MAX_CHILDREN, MAX_DEGREE, MAX_DEPTH, MAX_SLABS = 1024, 4096, 16, 16, 24, 64    # include/mtree.h
 LDS_SLOTS = 6144
+LR_MAX_DEGREE, LR_BLOCK = 15, 1024          # MTREE_LR_MAX_DEGREE, MTREE_LR_BLOCK
 MIN_SPAN = 1024              # a wave is given at least this many rows of a tree
 WORK_SLOTS = 1 << 26         # the slabs of one reduction stay below this many 8-byte slots (512 MiB)
 
@@ -50,6 +53,9 @@ SYMBOLS = {
     "mtree_work_len": (_i64, [_i32, _int, _int, _int]),
     "mtree_route": (_int, [_fp, _int, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mtree_reduce": (_int, [_fp, _int, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mtree_reduce_x_work_len": (_i64, [_i32, _i32, _int, _i64, _int]),
+    "mtree_reduce_x": (_int, [_fp, _int, _int, _vp, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mtree_values_len": (_i64, [_i32, _int, _int]),
     "mtree_sweep": (_int, [_fp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mtree_predict": (_int, [_fp, _int, _int, _int, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
@@ -60,8 +66,17 @@ load_library, _check = bind("mtree", SYMBOLS)
 
 def stat_cols(family: int, degree: int = 0):
     """(int64 columns, float64 columns, length of the posterior vector) of a family: include/mtree.h, mtree_stat_cols."""
+    tri = degree * (degree + 1) // 2
     return {BERNOULLI: (2, 0, 2), CATEGORICAL: (1 + degree, 0, degree), POISSON: (2, 1, 3), EXPONENTIAL: (1, 1, 2),
-            NORMAL: (1, 3, 5)}[family]
+            NORMAL: (1, 3, 5), LINREG: (1, tri + degree + 1, degree + tri + 3)}[family]
+
+
+def check_lr_degree(degree: int):
+    """The linear-regression sub-model's regressors and y share one 16-column MFMA tile (include/mtree.h)."""
+    if degree > LR_MAX_DEGREE:
+        raise EngineLimitError(
+            f"bayesml_amd.metatree supports SubModel=linearregression up to c_degree = {LR_MAX_DEGREE} in this version "
+            f"(got {degree}); bayesml itself has no such limit")
 
 
 @dataclass
@@ -121,11 +136,13 @@ def _ptr(t):
 
 
 class MtreePass:
-    """The tables of one forest on one device and the four entry points on them."""
+    """The tables of one forest on one device and the entry points on them."""
 
     def __init__(self, flat: FlatForest, family: int, degree: int, dim_cont: int, dim_cat: int, cat_card, h0, device=None):
         self.lib = load_library()
-        check_limits(flat.n_trees, flat.max_tree_nodes, flat.max_children, flat.max_depth, degree)
+        check_limits(flat.n_trees, flat.max_tree_nodes, flat.max_children, flat.max_depth, 0 if family == LINREG else degree)
+        if family == LINREG:
+            check_lr_degree(degree)
         self.device = gpu_device(device, "meta-tree engine")
         self.flat, self.family, self.degree = flat, int(family), int(degree)
         self.dim_cont, self.dim_cat = int(dim_cont), int(dim_cat)
@@ -145,9 +162,10 @@ class MtreePass:
         self.prob = torch.full((B,), 1.0 / B, dtype=torch.float64, device=dev)
         self.stat_int = torch.zeros(nodes, self.ni, dtype=torch.int64, device=dev)
         self.stat_real = torch.zeros(nodes, max(1, self.nr), dtype=torch.float64, device=dev)
-        self._values = torch.empty(nodes * max(2, self.degree), dtype=torch.float64, device=dev)
+        self._values = torch.empty(int(self.lib.mtree_values_len(nodes, self.family, self.degree)), dtype=torch.float64,
+                                   device=dev)
         self._bad = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._work = None
+        self._work = self._work_x = None
         self.struct = ForestStruct(B, nodes, len(flat.thr), flat.max_tree_nodes, flat.max_children, flat.max_depth,
                                    self.dim_cont, self.dim_cat, *(_ptr(self._tabs[k]) for k in
                                                                   ("tree_off", "feat", "child0", "nchild", "thr_off", "depth", "thr")))
@@ -193,6 +211,23 @@ class MtreePass:
             self._work = torch.empty(need, dtype=torch.int64, device=self.device)
         return self._work
 
+    def reduce_x(self, stop, x, y):
+        """The reduction of a family whose statistics need x (LINREG): x is [n, >= degree], read with its row stride."""
+        n = int(stop.shape[1])
+        S = slabs_for(n, self.flat.n_nodes, 1)
+        need = int(self.lib.mtree_reduce_x_work_len(self.flat.n_nodes, self.flat.n_trees, self.degree, n, S))
+        if need < 0:
+            raise EngineLimitError(f"bayesml_amd.metatree: a linear-regression update takes at most 2^31 - 1 rows (got {n}); "
+                                   "bayesml itself has no such limit")
+        if self._work_x is None or self._work_x.numel() < need:
+            self._work_x = None
+            self._work_x = torch.empty(need, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.mtree_reduce_x(ctypes.byref(self.struct), self.family, self.degree, stop.data_ptr(), _CODES[x.dtype],
+                                         x.data_ptr(), int(x.stride(0)), y.data_ptr(), n, S, self.stat_int.data_ptr(),
+                                         self.stat_real.data_ptr(), self._work_x.data_ptr(), stream_ptr(self.device))
+        _check(rc, "mtree_reduce_x")
+
     def reduce(self, stop, y):
         n = int(stop.shape[1])
         S = slabs_for(n, self.flat.n_nodes, self.ni + min(self.nr, 1))
@@ -220,9 +255,12 @@ class MtreePass:
         stop, _, bad = self.route(xc, xk)
         n, bad = int(stop.shape[1]), int(bad.cpu()[0])
         if bad == 0:
-            self.reduce(stop, y)
+            if self.family == LINREG:
+                self.reduce_x(stop, xc, y)
+            else:
+                self.reduce(stop, y)
             self.sweep()
-            self.launch_info = "mtree_route + mtree_reduce + mtree_sweep"
+            self.launch_info = f"mtree_route + mtree_reduce{'_x' if self.family == LINREG else ''} + mtree_sweep"
         return n, bad
 
     def predict(self, xc, xk, mode):
@@ -259,5 +297,5 @@ class MtreePass:
         return self.stat_int.cpu().numpy(), self.stat_real.cpu().numpy()[:, :self.nr]
 
     def close(self):
-        self._work = None
+        self._work = self._work_x = None
 

@@ -9,7 +9,12 @@ atomics, ``mtree_sweep`` folds, mixes and weights bottom-up in one launch.  ``pr
 given to a setter or to the constructor is flattened into them.  The tables stay on the host until an update or a
 prediction needs the engine, so setters and getters work without a GPU.
 
-Out of scope, each with an error that names it: ``SubModel=linearregression`` (``EngineLimitError``), ``alg_type``
+``SubModel=linearregression`` puts a Bayesian linear regression over all continuous features into every node
+(``sub_constants={'c_degree': c_dim_continuous}``, at most ``_mtree.LR_MAX_DEGREE``; anything else is an
+``EngineLimitError`` that says what to pass): ``mtree_reduce_x`` sorts every tree's rows by stop node and forms one X'X per
+node on the f64 MFMA, the sweep factors it per node.
+
+Out of scope, each with an error that names it: ``alg_type``
 ``'MTMCMC'`` / ``'REMTMCMC'`` (``NotImplementedError``) and plotting (``NotImplementedError``).  MTRF grows its forest with
 scikit-learn on the host, as the reference does; scikit-learn is imported in that path only.
 
@@ -33,10 +38,10 @@ CLF_MODELS = {bernoulli, categorical}
 REG_MODELS = {normal, linearregression, exponential, poisson}
 THRESHOLD_TYPES = {"even", "random"}
 _FAMILY = {bernoulli: _mtree.BERNOULLI, categorical: _mtree.CATEGORICAL, poisson: _mtree.POISSON,
-           exponential: _mtree.EXPONENTIAL, normal: _mtree.NORMAL}
+           exponential: _mtree.EXPONENTIAL, normal: _mtree.NORMAL, linearregression: _mtree.LINREG}
 _SUBMODEL_MSG = "SubModel must be bernoulli, categoricalpoisson, normal, exponential, or linearregression."
-_LR_MSG = ("SubModel=linearregression is not supported by bayesml_amd.metatree in this version (every node would need its "
-           "own X'X); bayesml itself has no such limit")
+_LR_MSG = ("SubModel=linearregression regresses y on all continuous features: pass sub_constants={'c_degree': "
+           "c_dim_continuous} with c_dim_continuous >= 1 (an intercept is a column of ones in x_continuous)")
 _INT_VECS_MSG = " must be a numpy.ndarray whose ndim >= 1 and dtype is int. Its values must be non-negative (including 0)."
 
 
@@ -61,8 +66,20 @@ class _Node:
         self.log_marginal_likelihood = log_marginal_likelihood
 
 
+def _check_lr_constants(c_dim_continuous, sub_constants):
+    """SubModel=linearregression: the reference hands x_continuous as it is to every node's learner (ref:1772-1774), so its
+    c_degree is c_dim_continuous.  A missing or different c_degree (a TypeError, or a DataFormatError at the first sample,
+    in the reference) is refused here, as is a degree beyond the engine's one-tile Gram pass."""
+    degree = sub_constants.get("c_degree") if isinstance(sub_constants, dict) else None
+    if degree is None:
+        raise EngineLimitError(_LR_MSG + "; sub_constants has no 'c_degree'")
+    if degree != c_dim_continuous:
+        raise EngineLimitError(_LR_MSG + f"; got c_degree = {degree} and c_dim_continuous = {c_dim_continuous}")
+    _mtree.check_lr_degree(int(degree))
+
+
 def _check_constants(self, c_dim_continuous, c_dim_categorical, c_max_depth, c_num_children_vec, c_num_assignment_vec,
-                     c_ranges, SubModel):
+                     c_ranges, SubModel, sub_constants):
     """The constants block that GenModel and LearnModel share (ref:196-242, 1178-1224)."""
     self.c_dim_continuous = _check.nonneg_int(c_dim_continuous, "c_dim_continuous", ParameterFormatError)
     self.c_dim_categorical = _check.nonneg_int(c_dim_categorical, "c_dim_categorical", ParameterFormatError)
@@ -93,7 +110,7 @@ def _check_constants(self, c_dim_continuous, c_dim_categorical, c_max_depth, c_n
     if SubModel not in MODELS:
         raise ParameterFormatError(_SUBMODEL_MSG)
     if SubModel is linearregression:
-        raise EngineLimitError(_LR_MSG)
+        _check_lr_constants(self.c_dim_continuous, sub_constants)
     self.SubModel = SubModel
     self._root_k_candidates = []
     for i in range(self.c_dim_features):
@@ -143,7 +160,7 @@ class GenModel(base.Generative):
                  c_ranges=None, SubModel=bernoulli, sub_constants={}, root=None, h_k_weight_vec=None, h_g=0.5,
                  sub_h_params={}, h_metatree_list=[], h_metatree_prob_vec=None, seed=None):
         _check_constants(self, c_dim_continuous, c_dim_categorical, c_max_depth, c_num_children_vec, c_num_assignment_vec,
-                         c_ranges, SubModel)
+                         c_ranges, SubModel, sub_constants)
         self.sub_constants = self.SubModel.GenModel(**sub_constants).get_constants()
         self.rng = np.random.default_rng(seed)
         self.h_k_weight_vec = np.ones(self.c_dim_features)
@@ -431,7 +448,9 @@ class GenModel(base.Generative):
             node = self.root
             while not node.leaf:
                 node = node.children[_child_index(node, self.c_dim_continuous, x_continuous[i], x_categorical[i])]
-            if self.SubModel is categorical:
+            if self.SubModel is linearregression:        # ref:426-428: the row's continuous features are the regressors
+                y[i] = np.ravel(node.sub_model.gen_sample(sample_size=1, x=x_continuous[i])[1])[0]
+            elif self.SubModel is categorical:
                 y[i] = np.ravel(node.sub_model.gen_sample(sample_size=1, onehot=False))[0]
             else:
                 y[i] = np.ravel(node.sub_model.gen_sample(sample_size=1))[0]
@@ -492,7 +511,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
                  c_ranges=None, SubModel=bernoulli, sub_constants={}, h0_k_weight_vec=None, h0_g=0.5, sub_h0_params={},
                  h0_metatree_list=[], h0_metatree_prob_vec=None, *, device=None):
         _check_constants(self, c_dim_continuous, c_dim_categorical, c_max_depth, c_num_children_vec, c_num_assignment_vec,
-                         c_ranges, SubModel)
+                         c_ranges, SubModel, sub_constants)
         self.sub_constants = self.SubModel.LearnModel(**sub_constants).get_constants()
         self._family = _FAMILY[self.SubModel]
         self._degree = int(self.sub_constants.get("c_degree", 0))
@@ -521,6 +540,10 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         f = self._family
         if f == _mtree.CATEGORICAL:
             return np.array(sub.hn_alpha_vec, dtype=float)
+        if f == _mtree.LINREG:        # [mu | upper triangle of Lambda, row-major | alpha | beta | n]
+            lam = np.asarray(sub.hn_lambda_mat, dtype=float)
+            return np.concatenate([np.asarray(sub.hn_mu_vec, dtype=float), lam[np.triu_indices(self._degree)],
+                                   [sub.hn_alpha, sub.hn_beta, sub._n]])
         if f == _mtree.NORMAL:
             return np.array([sub.hn_m, sub.hn_kappa, sub.hn_alpha, sub.hn_beta, sub._n], dtype=float)
         if f == _mtree.POISSON:
@@ -531,16 +554,32 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         """A scalar learner whose ``which`` hyperparameters are the post vector ``vec``."""
         sub = self._new_sub()
         f = self._family
-        vals = (np.array(vec),) if f == _mtree.CATEGORICAL else tuple(float(v) for v in vec[:4 if f == _mtree.NORMAL else 2])
+        if f == _mtree.LINREG:
+            mu, lam, alpha, beta, n = self._lr_parts(vec)
+            vals = (mu, lam, alpha, beta)
+        else:
+            vals = ((np.array(vec),) if f == _mtree.CATEGORICAL
+                    else tuple(float(v) for v in vec[:4 if f == _mtree.NORMAL else 2]))
         if which == "h0":
             sub.set_h0_params(*vals)
             return sub
         sub.set_hn_params(*vals)
-        if f == _mtree.NORMAL:
+        if f == _mtree.LINREG:
+            sub._n = int(n) if float(n).is_integer() else n
+        elif f == _mtree.NORMAL:
             sub._n = int(vec[4]) if float(vec[4]).is_integer() else vec[4]
         elif f == _mtree.POISSON:
             sub._sum_log_factorial = float(vec[2])
         return sub
+
+    def _lr_parts(self, vec):
+        """(mu, symmetric Lambda, alpha, beta, n) of a linear-regression post vector."""
+        D = self._degree
+        T = D * (D + 1) // 2
+        lam = np.zeros((D, D))
+        lam[np.triu_indices(D)] = vec[D:D + T]
+        lam = lam + np.triu(lam, 1).T
+        return np.array(vec[:D], dtype=float), lam, float(vec[D + T]), float(vec[D + T + 1]), vec[D + T + 2]
 
     def _prior_vec(self):
         """The engine's h0 vector: the sub-model's prior in the layout of a post vector."""
@@ -809,10 +848,18 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
                                      ParameterFormatError)
         return xc, xk, int((xc if xc is not None else xk).shape[0])
 
-    def _check_sample_y(self, y):
-        """The sub-model's own sample check (ref:2012-2017), on whatever holds y; returns it flat."""
+    def _check_sample_y(self, y, xc=None):
+        """The sub-model's own sample check (ref:2012-2017), on whatever holds y; returns it flat.  Linear regression checks
+        y against the rows of x_continuous (``xc``, [n, c_dim_continuous]); without ``xc`` (ref:3507-3508) y alone."""
         kind = _check.sample_kind(y)
         f = self._family
+        if f == _mtree.LINREG:
+            if xc is not None:
+                return self._new_sub()._check_sample(xc, y)[1]
+            if kind is None:
+                raise DataFormatError("y" + _check.SAMPLE_MSG["floats"])
+            y = y.reshape(-1)
+            return y if kind == "f" else (y.astype(float) if type(y) is np.ndarray else y.double())
         if kind is None or (f <= _mtree.POISSON and kind != "i"):
             key = {_mtree.BERNOULLI: "ints_of_01", _mtree.CATEGORICAL: "nonneg_ints", _mtree.POISSON: "nonneg_ints",
                    _mtree.EXPONENTIAL: "pos_floats", _mtree.NORMAL: "floats"}[f]
@@ -924,7 +971,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def update_posterior(self, x_continuous=None, x_categorical=None, y=None, alg_type="MTRF", **kwargs):
         """ref:2667-2818 in batch form; a refused sample changes nothing."""
         xc, xk, n = self._check_sample_x(x_continuous, x_categorical)
-        y = self._check_sample_y(y)
+        y = self._check_sample_y(y, xc)
         _check.shape_consistency(n, "x_continuous.shape[0] and x_categorical.shape[0]", y.shape[0], "y.shape[0]",
                                  ParameterFormatError)
         if alg_type in ("MTMCMC", "REMTMCMC"):
@@ -1096,7 +1143,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         return prediction
 
     def calc_pred_var(self):
-        if self.SubModel is not normal:
+        if self.SubModel not in (normal, linearregression):
             raise ParameterFormatError("SubModel must be normal or linearregression.")
         return self._predict(_mtree.PRED_VAR)[3]
 
@@ -1115,15 +1162,30 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         state = eng.get_state()
         out = np.zeros(self._p_n)
         subs = {}
+        if self._family == _mtree.LINREG:
+            x_host = np.asarray(xcd.cpu(), dtype=float)
+
+            def node_density(v, rows):
+                """Student-t with loc x . mu_v, scale lambda_v(x)^-1/2, df 2 alpha_v (ref: linearregression :722-730)."""
+                from scipy import stats
+                if v not in subs:
+                    subs[v] = self._lr_parts(state["post"][v])
+                mu, lam, alpha, beta, _ = subs[v]
+                x = x_host[rows]
+                lambdas = alpha / beta / (1.0 + np.sum(x.T * np.linalg.solve(lam, x.T), axis=0))
+                return stats.t.pdf(y[rows], loc=x @ mu, scale=1.0 / np.sqrt(lambdas), df=2.0 * alpha)
+        else:
+            def node_density(v, rows):
+                if v not in subs:
+                    subs[v] = self._sub_from(state["post"][v])
+                return subs[v]._calc_pred_density(y[rows])
         for b in range(paths.shape[0]):
             val = np.zeros(self._p_n)
             for j in range(paths.shape[2] - 1, -1, -1):
                 col = paths[b, :, j]
                 for v in np.unique(col[col >= 0]):
                     rows = col == v
-                    if v not in subs:
-                        subs[v] = self._sub_from(state["post"][v])
-                    own = subs[v]._calc_pred_density(y[rows])
+                    own = node_density(v, rows)
                     last = (paths[b, rows, j + 1] < 0) if j + 1 < paths.shape[2] else np.ones(rows.sum(), bool)
                     g = state["g"][v]
                     val[rows] = np.where(last, own, (1 - g) * own + g * val[rows])
