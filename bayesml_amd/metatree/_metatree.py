@@ -14,8 +14,14 @@ prediction needs the engine, so setters and getters work without a GPU.
 ``EngineLimitError`` that says what to pass): ``mtree_reduce_x`` sorts every tree's rows by stop node and forms one X'X per
 node on the f64 MFMA, the sweep factors it per node.
 
-Out of scope, each with an error that names it: ``alg_type``
-``'MTMCMC'`` / ``'REMTMCMC'`` (``NotImplementedError``) and plotting (``NotImplementedError``).  MTRF grows its forest with
+``alg_type='MTMCMC'`` / ``'REMTMCMC'`` learn the tree structure from the data: every chain's proposal grows level by level on
+the device (``_mtgrow.Grower``, include/mtgrow.h) in a complete tree of (C^(c_max_depth + 1) - 1) / (C - 1) slots (at most
+``_mtree.MAX_NODES``; at most ``_mtree.MAX_TREES`` chains; ``EngineLimitError`` beyond), is scored by the same route, reduce
+and sweep, and ``mtgrow_accept`` applies the Metropolis-Hastings test; the lists, the counts, g_max and the exchanges are host
+scalars.  Their random numbers are ADDRESSED Philox tables (``_mtgrow.node_table`` / ``aux_table``), not the reference's
+depth-first stream: a ``seed`` reproduces this package's chain and the reference's distribution, not the reference's chain.
+
+Out of scope, with an error that names it: plotting (``NotImplementedError``).  MTRF grows its forest with
 scikit-learn on the host, as the reference does; scikit-learn is imported in that path only.
 
 ``GenModel`` is host NumPy.
@@ -522,6 +528,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._hn = None               # _Forest or None; while the engine lives, its state is the engine's
         self._p_x = None
         self._last_map = None
+        self._mcmc_trace = None       # per step of the last MTMCMC / REMTMCMC fit: what mtgrow_accept returned, the exchanges
 
         self.h0_k_weight_vec = np.ones(self.c_dim_features)
         self.h0_g = 0.5
@@ -968,6 +975,242 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         trees, prob = self._merge_trees(trees, np.ones(n_estimators) / n_estimators)
         return self._flatten(trees, prob, None, self.hn_g)
 
+    # ---- MTMCMC / REMTMCMC (ref:2029-2665) --------------------------------------------------------------------------------
+    # The chains run on the growth engine (``_mtgrow.Grower``): a chain's tree is a table over the
+    # ``cap`` slots of the complete C-ary tree in heap order, the host keeps the lists, the counts, g_max and the exchanges.
+    # Random numbers are ADDRESSED (``_mtgrow.node_table`` / ``aux_table``), not streamed: a seed reproduces this package's
+    # chain and the reference's distribution, not the reference's chain.
+    def _mcmc_checks(self, threshold_type, num_chains=None):
+        """The preconditions the two algorithms share, with the reference's texts (ref:2044-2075, 2151-2184)."""
+        if np.any(self.c_num_children_vec != self.c_num_children_vec[0]):
+            raise ParameterFormatError("MTMCMC is supported only when all the elements of self.c_num_children_vec are the same. "
+                                       f"self.c_num_children_vec = {self.c_num_children_vec}.")
+        if np.any(self.c_num_assignment_vec > 0):
+            raise ParameterFormatError("MTMCMC is supported only when all the elements of self.c_num_assignment_vec are not "
+                                       f"positive. self.c_num_assignment_vec = {self.c_num_assignment_vec}.")
+        if not np.allclose(self.h0_k_weight_vec, self.h0_k_weight_vec[0]):
+            raise ParameterFormatError("MTMCMC is supported only when all the elements of self.h0_k_weight_vec are the same. "
+                                       f"self.h0_k_weight_vec = {self.h0_k_weight_vec}.")
+        if num_chains is not None:
+            _check.pos_int(num_chains, "num_chains", ParameterFormatError)
+        if threshold_type not in {"1d_kmeans", "sample_midpoint"}:
+            raise ParameterFormatError('threshold_type must be "1d_kmeans" or "sample_midpoint".')
+
+    def _grower(self, alg_type, num_chains, threshold_type, xc, xk, y):
+        """The growth engine of the installed factory: the real one, or the seam's ``grower`` (a factory without one cannot
+        run the chains)."""
+        from .. import _mtgrow
+        C = int(self.c_num_children_vec[0])
+        _mtgrow.capacity(C, self.c_max_depth, num_chains)          # EngineLimitError before anything is built
+        args = (self._family, self._degree, self.c_dim_continuous, self.c_dim_categorical,
+                self.c_num_children_vec[self.c_dim_continuous:], C, self.c_max_depth, self._prior_vec(), self._default_post(),
+                self.hn_g, self.h0_g, threshold_type, num_chains, xc, xk, y)
+        make = self._mtree_pass_factory
+        if make is None:
+            return _mtgrow.Grower(*args, device=self._device)
+        grower = getattr(make, "grower", None)
+        if grower is None:
+            raise NotImplementedError(f"alg_type='{alg_type}' needs an engine that grows trees (bayesml_amd._mtgrow); the "
+                                      "installed engine factory has none")
+        return grower(*args)
+
+    @staticmethod
+    def _mcmc_key(seed):
+        """The Philox key of a fit: ``seed`` itself where it is a non-negative integer below 2^64, fresh entropy for None,
+        and anything else NumPy seeds a generator with through ``numpy.random.SeedSequence``."""
+        from .. import _mtgrow
+        if seed is None:
+            return _mtgrow.fresh_key()
+        if isinstance(seed, (int, np.integer)) and 0 <= int(seed) < 2 ** 64:
+            return int(seed)
+        return int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+
+    def _same_tables(self, a, b, h=0):
+        """ref:1819-1843 on two trees' capacity tables."""
+        if a["feat"][h] < 0 or b["feat"][h] < 0:
+            return bool(a["feat"][h] < 0 and b["feat"][h] < 0)
+        if a["feat"][h] != b["feat"][h]:
+            return False
+        if a["feat"][h] < self.c_dim_continuous and not np.allclose(a["thr"][h], b["thr"][h]):
+            return False
+        C = int(self.c_num_children_vec[0])
+        return all(self._same_tables(a, b, C * h + 1 + i) for i in range(C))
+
+    def _forest_from_tables(self, trees, prob):
+        """ref:1845-1856 and the flattening: equal trees are merged (the earlier hands its probability to the later), then
+        every tree's reachable slots become breadth-first tables with the state the engine left in them."""
+        trees, prob = list(trees), np.array(prob, dtype=float)
+        for i in range(len(trees)):
+            for j in range(i + 1, len(trees)):
+                if self._same_tables(trees[i], trees[j]):
+                    trees[i] = None
+                    prob[j] += prob[i]
+                    prob[i] = -1
+                    break
+        trees, prob = [t for t in trees if t is not None], prob[prob > -0.5]
+        C = int(self.c_num_children_vec[0])
+        tree_off, feat, child0, nchild, thr_off, depth, thr = [0], [], [], [], [], [], []
+        g, post, lml, lcm = [], [], [], []
+        for t in trees:
+            order, base_i, i = [(0, 0)], len(feat), 0
+            while i < len(order):
+                h, d = order[i]
+                k = int(t["feat"][h])
+                feat.append(k)
+                depth.append(d)
+                g.append(0.0 if d == self.c_max_depth else float(t["g"][h]))
+                post.append(t["post"][h])
+                lml.append(0.0 if np.isnan(t["lml"][h]) and h > 0 else float(t["lml"][h]))    # (an empty child: ref:2323)
+                lcm.append(float(t["lcm"][h]))
+                if k < 0:
+                    child0.append(0)
+                    nchild.append(0)
+                    thr_off.append(-1)
+                else:
+                    child0.append(base_i + len(order))
+                    nchild.append(C)
+                    if k < self.c_dim_continuous:
+                        thr_off.append(len(thr))
+                        thr.extend(np.asarray(t["thr"][h], dtype=float)[:C + 1])
+                    else:
+                        thr_off.append(-1)
+                    order.extend((C * h + 1 + c, d + 1) for c in range(C))
+                i += 1
+            tree_off.append(len(feat))
+        flat = _mtree.FlatForest(np.array(tree_off, np.int32), np.array(feat, np.int32), np.array(child0, np.int32),
+                                 np.array(nchild, np.int32), np.array(thr_off, np.int32), np.array(depth, np.int32),
+                                 np.array(thr, np.float64))
+        _mtree.check_limits(flat.n_trees, flat.max_tree_nodes, flat.max_children, flat.max_depth, self._degree)
+        state = dict(g=np.array(g, float), post=np.array(post, float).reshape(len(g), -1), lml=np.array(lml, float),
+                     lcm=np.array(lcm, float), prob=prob)
+        return _Forest(flat, state)
+
+    def _mtmcmc(self, xc, xk, y, burn_in=100, num_metatrees=500, g_max=0.0, rho=0.99, phi=0.999, p_obj=0.3,
+                threshold_type="1d_kmeans", seed=None):
+        """ref:2029-2133: one Metropolis-Hastings chain over tree structures with an adaptive g_max during burn-in."""
+        from .. import _mtgrow
+        self._mcmc_checks(threshold_type)
+        key = self._mcmc_key(seed)
+        grower = self._grower("MTMCMC", 1, threshold_type, xc, xk, y)
+        try:
+            _, bad = grower.start(_mtgrow.node_table(key, 0, 1, grower.cap))
+            if bad > 0:
+                self._raise_bad(grower.xk)
+            trees, counts = [grower.snapshot(0)], [1]
+            if self.c_dim_features == 1:
+                return self._forest_from_tables(trees, np.array([1.0]))
+            proposed = accepted = 1
+            numerator = denominator = 0.0
+            trace = self._mcmc_trace = dict(out=[], g_max=[])
+            g_acc = g_den = 0.0
+
+            def step():
+                nonlocal proposed, accepted, numerator, denominator
+                out = grower.step(_mtgrow.node_table(key, proposed, 1, grower.cap), _mtgrow.aux_table(key, proposed, 1), None,
+                                  g_max)
+                trace["out"].append(out)
+                numerator *= rho
+                denominator = denominator * rho + 1
+                if out[0, 0] > 0:
+                    trees.append(grower.snapshot(0))
+                    counts.append(1)
+                    accepted += 1
+                    numerator += 1
+                else:
+                    counts[-1] += 1
+                proposed += 1
+                print(f"\r{proposed}(accepted:{accepted})", end="")
+
+            print(f"brun_in: {burn_in}")
+            while proposed < burn_in:
+                step()
+                p_hat = numerator / denominator                   # _update_g_max (ref:2623-2634)
+                g_new = g_max * p_obj / p_hat if p_hat > p_obj else 1.0 - (1.0 - g_max) * (1.0 - p_obj) / (1.0 - p_hat)
+                g_acc = g_acc * phi + g_new
+                g_den = g_den * phi + 1
+                g_max = g_acc / g_den
+                trace["g_max"].append(g_max)
+            print()
+            tmp = accepted - 1
+            counts[-1] = 1
+            print(f"burn_in + num_metatrees: {burn_in + num_metatrees}")
+            while proposed < burn_in + num_metatrees:
+                step()
+            print()
+            prob = np.array(counts[tmp:], dtype=float)
+            return self._forest_from_tables(trees[tmp:], prob / prob.sum())
+        finally:
+            grower.close()
+
+    def _remtmcmc(self, xc, xk, y, burn_in=100, num_metatrees=500, num_chains=8, g_max=0.9, beta_vec=None, num_interval=10,
+                  num_exchange=4, threshold_type="1d_kmeans", seed=None):
+        """ref:2135-2256: num_chains tempered chains with replica exchange; only the last chain's trees are kept."""
+        from .. import _mtgrow
+        self._mcmc_checks(threshold_type, num_chains)
+        B = int(num_chains)
+        beta = (np.arange(B) + 1) / B
+        if beta_vec is not None:
+            beta[:] = beta_vec
+            if np.any(beta < 0) or np.any(beta > 1):
+                raise ParameterFormatError(f"All the elements of beta_vec must be in [0,1] beta_vec = {beta_vec}.")
+        num_interval = _check.pos_int(num_interval, "num_interval", ParameterFormatError)
+        num_exchange = _check.pos_int(num_exchange, "num_exchange", ParameterFormatError)
+        key = self._mcmc_key(seed)
+        grower = self._grower("REMTMCMC", B, threshold_type, xc, xk, y)
+        try:
+            l_lasts, bad = grower.start(_mtgrow.node_table(key, 0, B, grower.cap))
+            if bad > 0:
+                self._raise_bad(grower.xk)
+            l_lasts = np.array(l_lasts, dtype=float)
+            trees, counts = [grower.snapshot(B - 1)], [1]          # the last chain's list; the others keep one tree each
+            if self.c_dim_features == 1:
+                return self._forest_from_tables(trees, np.array([1.0]))
+            t = 0
+            trace = self._mcmc_trace = dict(out=[], exchange=[])
+
+            def step(i):
+                nonlocal t
+                t += 1
+                aux = _mtgrow.aux_table(key, t, B, num_exchange)
+                out = grower.step(_mtgrow.node_table(key, t, B, grower.cap), aux[:B], beta, g_max)
+                trace["out"].append(out)
+                ok = out[:, 0] > 0
+                l_lasts[ok] = out[ok, 1]
+                if ok[B - 1]:
+                    trees.append(grower.snapshot(B - 1))
+                    counts.append(1)
+                else:
+                    counts[-1] += 1
+                if B > 1 and i % num_interval == 0:                # _replica_exchange_memory_efficient (ref:2580-2610)
+                    trace["exchange"].append(-1)
+                    for e in range(num_exchange):
+                        j = min(B - 2, int(np.floor(aux[B + 2 * e] * (B - 1))))
+                        if aux[B + 2 * e + 1] < np.exp(l_lasts[j] * beta[j + 1] + l_lasts[j + 1] * beta[j]
+                                                       - l_lasts[j] * beta[j] - l_lasts[j + 1] * beta[j + 1]):
+                            grower.swap(j)
+                            trace["exchange"].append(j)
+                            l_lasts[[j, j + 1]] = l_lasts[[j + 1, j]]
+                            if j == B - 2:                         # the last chain takes chain j's tree as a new entry
+                                counts[-1] -= 1
+                                trees.append(grower.snapshot(B - 1))
+                                counts.append(1)
+                print(f"\r{i}", end="")
+
+            print(f"brun_in: {burn_in}")
+            for i in range(burn_in):
+                step(i)
+            print()
+            tmp = len(counts) - 1
+            counts[-1] = 1
+            print(f"num_metatrees: {num_metatrees}")
+            for i in range(num_metatrees):
+                step(i)
+            print()
+            prob = np.array(counts[tmp:], dtype=float)
+            return self._forest_from_tables(trees[tmp:], prob / prob.sum())
+        finally:
+            grower.close()
+
     def update_posterior(self, x_continuous=None, x_categorical=None, y=None, alg_type="MTRF", **kwargs):
         """ref:2667-2818 in batch form; a refused sample changes nothing."""
         xc, xk, n = self._check_sample_x(x_continuous, x_categorical)
@@ -975,8 +1218,11 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         _check.shape_consistency(n, "x_continuous.shape[0] and x_categorical.shape[0]", y.shape[0], "y.shape[0]",
                                  ParameterFormatError)
         if alg_type in ("MTMCMC", "REMTMCMC"):
-            raise NotImplementedError(f"alg_type='{alg_type}' is not supported by bayesml_amd.metatree in this version "
-                                      "(sequential Metropolis-Hastings over tree structures)")
+            if isinstance(xk, np.ndarray):
+                self._check_values(xk)
+            run = self._mtmcmc if alg_type == "MTMCMC" else self._remtmcmc
+            self._set_hn(run(xc, xk, y, **kwargs))
+            return self
         if alg_type not in ("MTRF", "given_MT"):
             return self                     # (the reference falls through its chain of elifs, ref:2806-2818)
         if alg_type == "MTRF" or isinstance(xk, np.ndarray):
