@@ -42,11 +42,12 @@ load_library, _check = bind("ctree", SYMBOLS)
 
 
 def check_limit(c_k: int, c_d_max: int):
-    """Raised at model construction: the deepest count table has k^(D+1) slots and there is no sparse path behind the
-    dense tables (the reference has no such limit)."""
+    """Raised at model construction: the deepest count table has k^(D+1) slots (the reference has no such limit; the
+    sparse tables of ``_ctsp`` are opt-in, ``LearnModel(..., tables="sparse")``)."""
     if c_k > MAX_K or c_k ** (c_d_max + 1) > MAX_SLOTS or c_d_max > 24:
         raise EngineLimitError(f"bayesml_amd.contexttree supports c_k <= {MAX_K} and c_k ** (c_d_max + 1) <= {MAX_SLOTS} in "
-                               f"this version (got c_k = {c_k}, c_d_max = {c_d_max}); bayesml itself has no such limit")
+                               f"this version (got c_k = {c_k}, c_d_max = {c_d_max}); bayesml itself has no such limit, and "
+                               f"tables=\"sparse\" goes to ceil(log2 c_k) * c_d_max <= 63")
 
 
 def offsets(k: int, D: int):

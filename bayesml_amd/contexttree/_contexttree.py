@@ -9,6 +9,10 @@ read of ``[n | bad]`` decides whether the sample is accepted, and ``ctree_sweep`
 (``calc_pred_dist``, ``pred_and_update``) gathers its D + 1 rows and works on the host.  ``hn_root`` is a property that
 materialises the ``_Node`` tree from the tables on demand; a tree given to a setter is scattered into them.
 
+With ``tables="sparse"`` the posterior lives in per-level hash tables that hold only the nodes that exist
+(``_ctsp.SparseCtreePass``, the same update by the ``ctsp_*`` entry points); nodes are then addressed by (level, key), and
+that index arithmetic is in ``_sparse``.
+
 ``GenModel`` is host NumPy: the chain is sequential and short.
 """
 from __future__ import annotations
@@ -17,7 +21,8 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _ctree, base
+from .. import _check, _ctree, _ctsp, base
+from . import _sparse
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _INT_VEC_MSG = " must be a 1-dimensional numpy.ndarray whose dtype is int. Its values must be non-negative (including 0)."
@@ -195,7 +200,9 @@ class GenModel(base.Generative):
 class LearnModel(base.Posterior, base.PredictiveMixin):
     """Posterior and predictive distribution (ref:422-1067).  Positional parameters are the reference's; keyword-only
     ``device`` selects the GPU.  The dense tables limit the shape to ``c_k <= 256`` and ``c_k ** (c_d_max + 1) <= 2 ** 24``
-    (``EngineLimitError`` beyond; the reference has no such limit).
+    (``EngineLimitError`` beyond; the reference has no such limit).  Keyword-only ``tables="sparse"`` stores only the nodes
+    that exist, in per-level hash tables on the device (``_ctsp.SparseCtreePass``): the limit is then
+    ``ceil(log2 c_k) * c_d_max <= 63`` and the memory the nodes take.  ``tables="dense"`` is the default.
 
     The engine, and with it the GPU, is first needed when a posterior tree exists: at the first ``update_posterior`` or
     ``pred_and_update`` - or already in the constructor (and in ``set_h0_params`` / ``set_hn_params``) when a tree is given
@@ -203,16 +210,20 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     ``EngineUnavailableError``; a model without a tree is built on the host alone."""
 
     _ctree_pass_factory = None        # private test seam (tests/fake_contexttree_engine.py)
+    _sparse = False                   # (a model pickled before the keyword existed is dense)
 
-    def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, device=None):
+    def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, tables="dense", device=None):
         self.c_k = _check.pos_int(c_k, "c_k", ParameterFormatError)
         self.c_d_max = _check.pos_int(c_d_max, "c_d_max", ParameterFormatError)
-        _ctree.check_limit(self.c_k, self.c_d_max)
+        if tables not in ("dense", "sparse"):
+            raise ParameterFormatError("tables must be \"dense\" or \"sparse\"")
+        self._sparse = tables == "sparse"
+        (_ctsp if self._sparse else _ctree).check_limit(self.c_k, self.c_d_max)
         self._device = device
         self._engine = None
         self._saved_tables = None
         self._has_root = False
-        self._off = _ctree.offsets(self.c_k, self.c_d_max)
+        self._off = None if self._sparse else _ctree.offsets(self.c_k, self.c_d_max)
 
         self.h0_g = h0_g
         self.h0_beta_vec = np.ones(self.c_k) / 2
@@ -224,6 +235,11 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
 
     # ---- the engine and its tables ---------------------------------------------------------------------------------------
     def _eng(self):
+        if self._engine is None and self._sparse:
+            self._engine = _sparse.make_engine(self)
+            if self._saved_tables is not None:
+                self._engine.set_nodes(self._saved_tables)
+                self._saved_tables = None
         if self._engine is None:
             make = self._ctree_pass_factory
             self._engine = (make(self.c_k, self.c_d_max) if make is not None
@@ -236,12 +252,16 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def __getstate__(self):
         state = dict(self.__dict__)
         if self._engine is not None and self._has_root:
-            state["_saved_tables"] = self._engine.get_tables()
+            state["_saved_tables"] = self._engine.get_nodes() if self._sparse else self._engine.get_tables()
         state["_engine"] = None
         return state
 
     def get_constants(self):
         return {"c_k": self.c_k, "c_d_max": self.c_d_max}
+
+    def _root_index(self):
+        """The root as the engine addresses it: table index 0, or (level, key) = (0, 0)."""
+        return (0, 0) if self._sparse else 0
 
     def _default_g(self, depth):
         return 0.0 if depth == self.c_d_max else self.hn_g
@@ -252,6 +272,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         or ``None`` before the first update."""
         if not self._has_root:
             return None
+        if self._sparse:
+            return _sparse.hn_root(self, _Node)
         t = self._eng().get_tables()
         k, off, level = self.c_k, self._off, {}
         for d in range(self.c_d_max + 1):
@@ -331,15 +353,18 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if hn_root is not None:
             if type(hn_root) is not _Node:
                 raise ParameterFormatError("hn_root must be an instance of contexttree._Node")
-            eng = self._eng()
-            if not self._has_root:
-                eng.clear()
-            t = eng.get_tables()
-            if not self._has_root:
-                t["exists"][0], t["g"][0], t["beta"][0], t["leaf"][0] = 1, 0.5, 0.5, 0
-            self._scatter_tree(t, 0, 0, hn_root)
-            eng.set_tables(t)
-            self._has_root = True
+            if self._sparse:
+                _sparse.set_hn_root(self, hn_root)
+            else:
+                eng = self._eng()
+                if not self._has_root:
+                    eng.clear()
+                t = eng.get_tables()
+                if not self._has_root:
+                    t["exists"][0], t["g"][0], t["beta"][0], t["leaf"][0] = 1, 0.5, 0.5, 0
+                self._scatter_tree(t, 0, 0, hn_root)
+                eng.set_tables(t)
+                self._has_root = True
         self.calc_pred_dist(np.zeros(self.c_d_max, dtype=int))
         return self
 
@@ -378,8 +403,10 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         eng = self._eng()
         if not self._has_root:
             eng.clear()
-            eng.scatter([0], [self.hn_g], [self.hn_beta_vec], [1], [0])
+            eng.scatter([self._root_index()], [self.hn_g], [self.hn_beta_vec], [1], [0])
             self._has_root = True
+        if self._sparse:
+            return _sparse.map_tree(self, _Node)
         ml = eng.map_leaf(self.hn_g)
         t = eng.get_tables()
         k, D, off = self.c_k, self.c_d_max, self._off
@@ -426,6 +453,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def _path(self, x):
         """The D + 1 (or fewer) rows that the context before x[-1] selects, missing ones created with the defaults as
         ref:956-965 does.  Returns (indices, g, beta, leaf)."""
+        if self._sparse:
+            return _sparse.path(self, x)
         i = x.shape[0] - 1
         depth = min(i, self.c_d_max)
         idx, key = [0], 0
@@ -466,7 +495,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         eng = self._eng()
         if not self._has_root:
             eng.clear()
-            eng.scatter([0], [self.hn_g], [self.hn_beta_vec], [1], [0])
+            eng.scatter([self._root_index()], [self.hn_g], [self.hn_beta_vec], [1], [0])
             self._has_root = True
         idx, g, beta, leaf = self._path(x)
         a = int(x[-1])

@@ -15,6 +15,8 @@
 //     forms its counts as child sums (+ the head sample), then the Dirichlet-multinomial ratio and the two-way mixture of
 //     DESIGN.md "Context tree".  A node whose counts are all zero returns before it writes any state.
 // (c) map_level_kernel: the same level structure for the MAP recursion.
+// The non-template kernels are `static`: ctsp_kernels.h includes this header for the node arithmetic, in a second
+// translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,8 +85,9 @@ __global__ __launch_bounds__(kThreads) void count_kernel(const T* __restrict__ x
 
 // out = [ n | bad | table ]: slot 1 + j of the S slabs added in slab order.  The global-atomic path has slab_len = 1 (only
 // `bad`) and its table is already in place.
-__global__ __launch_bounds__(kThreads) void count_combine_kernel(const int64_t* __restrict__ work, int S, int64_t slab_len,
-                                                                 int64_t n, int64_t* __restrict__ out) {
+static __global__ __launch_bounds__(kThreads) void count_combine_kernel(const int64_t* __restrict__ work, int S,
+                                                                        int64_t slab_len, int64_t n,
+                                                                        int64_t* __restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (j == 0) out[0] = n;
     if (j >= slab_len) return;
@@ -206,7 +209,35 @@ __device__ inline double dm_row_and_update(int k, const int64_t* __restrict__ c,
     return post.value() - prior.value();
 }
 
-__global__ __launch_bounds__(kThreads) void sweep_deepest_kernel(int k, int64_t nkeys, const int64_t* __restrict__ cnt,
+// A node above the maximal depth with at least one sample: prior weight g0, children's log-weights summed to S, head sample
+// `hs` (-1: none).  beta <- beta + c; returns the new g and the node's own log-weight.  Shared with ctsp_kernels.h.
+struct NodeResult {
+    double g, lnw;
+};
+__device__ inline NodeResult inner_node_update(int k, const int64_t* __restrict__ c, double* __restrict__ b,
+                                               const double* __restrict__ hn_beta, bool ex, int hs, double g0, double S) {
+    double lead = 0.0;
+    if (hs >= 0) {
+        double sb0 = 0.0;
+        for (int a = 0; a < k; ++a) sb0 += ex ? b[a] : hn_beta[a];
+        lead = log((ex ? b[hs] : hn_beta[hs]) / sb0);
+    }
+    const double L = dm_row_and_update(k, c, b, hn_beta, ex, hs);
+    double mix, gn;
+    if (!(g0 > 0.0)) {
+        mix = L, gn = 0.0;
+    } else {
+        const double A = log1p(-g0) + L, B = log(g0) + S;
+        const double t = A - B;       // logaddexp(A, B)
+        mix = t == 0.0 ? A + 0.6931471805599453 : t > 0.0 ? A + log1p(exp(-t)) : B + log1p(exp(t));
+        // B - mix = -log1p(e^t).  Next to 1 (t < 0) that difference is known to an ulp of B only, which would cost 1 - g
+        // its digits; 1 / (1 + e^t) keeps them.
+        gn = t > 0.0 ? exp(B - mix) : 1.0 / (1.0 + exp(t));
+    }
+    return {gn, lead + mix};
+}
+
+static __global__ __launch_bounds__(kThreads) void sweep_deepest_kernel(int k, int64_t nkeys, const int64_t* __restrict__ cnt,
                                                                  double* __restrict__ beta, double* __restrict__ g,
                                                                  uint8_t* __restrict__ exists,
                                                                  const double* __restrict__ hn_beta,
@@ -229,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void sweep_deepest_kernel(int k, int64_t 
 }
 
 // Level d < D.  cnt_child / lnw_child are level d + 1's (k * nkeys keys); cnt, lnw, beta, g, exists are level d's.
-__global__ __launch_bounds__(kThreads) void sweep_level_kernel(int k, int d, int64_t nkeys,
+static __global__ __launch_bounds__(kThreads) void sweep_level_kernel(int k, int d, int64_t nkeys,
                                                                const int64_t* __restrict__ cnt_child,
                                                                int64_t* __restrict__ cnt,
                                                                const double* __restrict__ lnw_child,
@@ -268,36 +299,17 @@ __global__ __launch_bounds__(kThreads) void sweep_level_kernel(int k, int d, int
     double S = 0.0;
     for (int ch = 0; ch < k; ++ch) S += lnw_child[s + (int64_t)ch * nkeys];
     const bool ex = exists[s] != 0;
-    const double g0 = ex ? g[s] : hn_g;
-    double* b = beta + s * k;
-    double lead = 0.0;
-    if (hs >= 0) {
-        double sb0 = 0.0;
-        for (int a = 0; a < k; ++a) sb0 += ex ? b[a] : hn_beta[a];
-        lead = log((ex ? b[hs] : hn_beta[hs]) / sb0);
-    }
-    const double L = dm_row_and_update(k, c, b, hn_beta, ex, hs);
-    double mix, gn;
-    if (!(g0 > 0.0)) {
-        mix = L, gn = 0.0;
-    } else {
-        const double A = log1p(-g0) + L, B = log(g0) + S;
-        const double t = A - B;       // logaddexp(A, B)
-        mix = t == 0.0 ? A + 0.6931471805599453 : t > 0.0 ? A + log1p(exp(-t)) : B + log1p(exp(t));
-        // B - mix = -log1p(e^t).  Next to 1 (t < 0) that difference is known to an ulp of B only, which would cost 1 - g
-        // its digits; 1 / (1 + e^t) keeps them.
-        gn = t > 0.0 ? exp(B - mix) : 1.0 / (1.0 + exp(t));
-    }
-    g[s] = gn;
+    const NodeResult r = inner_node_update(k, c, beta + s * k, hn_beta, ex, hs, ex ? g[s] : hn_g, S);
+    g[s] = r.g;
     exists[s] = 1;
-    lnw[s] = lead + mix;
+    lnw[s] = r.lnw;
 }
 
 // ---- (c) ------------------------------------------------------------------------------------------------------------------
 // Level d of the MAP sweep.  pw_here = hn_g^((k^(D-d) - 1)/(k - 1) - 1) prices a missing child of a node of this level,
 // pw_parent the same one level up (a missing node of this level whose parent exists).  *_child / *_parent are the
 // neighbouring levels' tables (unused pointers at d = D and d = 0).
-__global__ __launch_bounds__(kThreads) void map_level_kernel(int k, int d, int D, int64_t nkeys, const double* __restrict__ g,
+static __global__ __launch_bounds__(kThreads) void map_level_kernel(int k, int d, int D, int64_t nkeys, const double* __restrict__ g,
                                                              const uint8_t* __restrict__ exists,
                                                              const uint8_t* __restrict__ exists_child,
                                                              const double* __restrict__ val_child,

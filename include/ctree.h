@@ -23,6 +23,7 @@
  *
  * Limit: k <= CTREE_MAX_K and k^(D+1) <= CTREE_MAX_SLOTS (the deepest count table).  Beyond it every entry point returns
  * CTREE_EUNSUPPORTED (k = 1: D <= 24).  The reference has no such limit.
+ * (ctsp.h is the same update on sparse per-level hash tables, for shapes beyond this limit.)
  */
 #ifndef CTREE_H
 #define CTREE_H
