@@ -5,7 +5,8 @@ The reference keeps the posterior as a tree of Python ``_Node`` objects and walk
 the posterior lives in dense per-level tables on the device (``_ctree.CtreePass``) and ``update_posterior`` is the batch
 form of DESIGN.md "Context tree": ``ctree_count`` counts every (context, symbol) pair of the sample where it lies, one host
 read of ``[n | bad]`` decides whether the sample is accepted, and ``ctree_sweep`` applies the update level by level.
-``estimate_params`` runs ``ctree_map`` and builds only the pruned MAP tree.  What touches one root-to-leaf path
+``estimate_params`` runs ``ctree_map`` and builds only the pruned MAP tree.  ``pred_and_update_sequence`` is the per-symbol
+loop of ``pred_and_update`` over a whole sample in its level-wise form (``_ctseq.SequencePass``).  What touches one root-to-leaf path
 (``calc_pred_dist``, ``pred_and_update``) gathers its D + 1 rows and works on the host.  ``hn_root`` is a property that
 materialises the ``_Node`` tree from the tables on demand; a tree given to a setter is scattered into them.
 
@@ -21,7 +22,7 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _ctree, _ctsp, base
+from .. import _check, _ctree, _ctseq, _ctsp, base
 from . import _sparse
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
@@ -210,6 +211,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     ``EngineUnavailableError``; a model without a tree is built on the host alone."""
 
     _ctree_pass_factory = None        # private test seam (tests/fake_contexttree_engine.py)
+    _ctseq_pass_factory = None        # private test seam (tests/contexttree_seq_oracle.py)
+    _seq_pass = None
     _sparse = False                   # (a model pickled before the keyword existed is dense)
 
     def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, tables="dense", device=None):
@@ -254,6 +257,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if self._engine is not None and self._has_root:
             state["_saved_tables"] = self._engine.get_nodes() if self._sparse else self._engine.get_tables()
         state["_engine"] = None
+        state.pop("_seq_pass", None)
         return state
 
     def get_constants(self):
@@ -510,3 +514,56 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.p_theta_vec[:] = p
         eng.scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
         return self.make_prediction(loss=loss)
+
+    def pred_and_update_sequence(self, x, loss="KL", *, code_length=False, chunk_bytes=None):
+        """``[pred_and_update(x[:i + 1], loss) for i in range(n)]`` in one device pass per level (``_ctseq.SequencePass``,
+        DESIGN.md "Sequential prediction"); the posterior is left as that loop leaves it.
+
+        ``x`` is accepted and refused as ``update_posterior`` does it; a refused sample changes nothing.  The return is
+        float64 ``[n, c_k]`` for ``loss="KL"`` and int64 ``[n]`` (the first maximum) for ``"0-1"``: NumPy arrays for a
+        NumPy ``x``, tensors on the model's device for a device tensor.  With ``code_length=True`` it is
+        ``(prediction, nats)``, ``nats[i] = -ln p(x[i] | x[:i])`` float64 ``[n]``.  ``loss=None`` needs
+        ``code_length=True`` and returns ``nats`` alone; no ``[n, c_k]`` buffer exists then and ``p_theta_vec`` is left
+        untouched (otherwise it becomes the last row).  ``chunk_bytes`` bounds the workspace (default 256 MiB): positions
+        are processed in chunks of ``_ctseq.plan_chunks(...)`` positions, in order, with the state carried by the tables,
+        so one call equals successive calls on the same pieces bit for bit.  Within a chunk a node's log-odds are
+        carried in binary64 and stored as ``h_g`` at the chunk's end; an ``h_g`` that rounds to exactly 0 or 1 there stays,
+        as it does between two calls of the reference.  Dense tables only."""
+        if self._sparse:
+            raise NotImplementedError("pred_and_update_sequence does not support tables=\"sparse\" in this version; "
+                                      "build the model with tables=\"dense\"")
+        if loss is None:
+            if not code_length:
+                raise CriteriaError("loss=None returns the code lengths alone: pass code_length=True with it.")
+        elif not (isinstance(loss, str) and loss in ("KL", "0-1")):
+            raise CriteriaError("Unsupported loss function! This function supports \"0-1\" and \"KL\".")
+        if _check._is_int(x) and x >= 0:
+            x = np.asarray([x])
+        if _check.sample_kind(x) != "i":
+            raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
+        if (x.numel() if hasattr(x, "numel") else x.size) == 0:
+            np.max(np.zeros(0))          # the reference's x.max() of an empty sample: ValueError
+        as_numpy = isinstance(x, np.ndarray)
+        eng = self._eng()
+        xd = eng.adopt(x)
+        n, bad = (int(v) for v in eng.count(xd)[:2].cpu())
+        if bad > 0:
+            if eng.any_negative(xd):
+                raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
+            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+        if self._seq_pass is None:
+            make = self._ctseq_pass_factory
+            self._seq_pass = make(eng) if make is not None else _ctseq.SequencePass(eng)
+        if not self._has_root:
+            eng.clear()
+        want = {"KL": "rows", "0-1": "argmax", None: None}[loss]
+        pred, nats, last = self._seq_pass.run(xd, self.hn_g, self.hn_beta_vec, want, bool(code_length), chunk_bytes)
+        self._has_root = True
+        if last is not None:
+            self.p_theta_vec[:] = last.cpu().numpy()
+        if as_numpy:
+            pred = None if pred is None else pred.cpu().numpy()
+            nats = None if nats is None else nats.cpu().numpy()
+        if loss is None:
+            return nats
+        return (pred, nats) if code_length else pred
