@@ -124,3 +124,57 @@ def data_pass(obj, D):
         from ._regression import RegressionPass
         obj._engine = RegressionPass(D, obj._device)
     return obj._engine
+
+
+# ---- sequential prediction (include/regseq.h; DESIGN.md 4f, "Sequential prediction") -----------------------------------------
+def seq_pass(obj, D):
+    """The model's RegressionSeqPass, or the stand-in of the test seam ``obj._regseq_pass_factory``
+    (tests/regression_seq_oracle.py); as ``data_pass``, no fallback."""
+    if obj._regseq_pass_factory is not None:
+        return obj._regseq_pass_factory(D)
+    if obj._seq_engine is None:
+        from ._regseq import RegressionSeqPass
+        obj._seq_engine = RegressionSeqPass(D, obj._device)
+    return obj._seq_engine
+
+
+def check_sequence_loss(loss, code_length):
+    if loss is None:
+        if not code_length:
+            raise CriteriaError("loss=None returns the code lengths alone: pass code_length=True with it.")
+    elif not (isinstance(loss, str) and loss in ("squared", "0-1", "abs", "KL")):
+        raise CriteriaError(_LOSS_MSG)
+
+
+def fetch(obj):
+    """``obj._p`` = (p_ms, p_lambdas) as float64 ndarrays: device tensors are copied on the first read."""
+    if not isinstance(obj._p[0], np.ndarray):
+        obj._p = tuple(t.detach().to("cpu").double().numpy() for t in obj._p)
+    return obj._p
+
+
+def pred_and_update_sequence(obj, n, run, update, as_numpy, loss, code_length):
+    """What the two models' ``pred_and_update_sequence`` share, after the sample has been accepted: ``run(start)`` gives
+    (p_ms, p_lambdas, nats) of the n rows as device tensors from the state ``start`` (``_regseq.start_state``) and
+    ``update()`` is the model's own ``update_posterior`` on the same sample, so that ``hn_*`` are its bits.  Leaves
+    ``obj._p`` (on the device until first read) and ``obj.p_nus`` and returns what the method returns."""
+    from ._regseq import start_state
+    alpha0 = float(obj.hn_alpha)
+    if n > 0:
+        p_m, p_lambda, nats = run(start_state(obj.hn_mu_vec, obj.hn_lambda_mat, obj.hn_alpha, obj.hn_beta))
+        update()
+    else:                    # no rows: nothing to predict, nothing to learn, nothing to launch
+        import torch
+        p_m = p_lambda = nats = torch.zeros(0, dtype=torch.float64)
+    obj._p = (p_m, p_lambda)
+    # the device's own expression for alpha_i: alpha_0 + (rows before i) / 2, one rounding each
+    obj.p_nus = 2.0 * (alpha0 + np.arange(n) / 2.0)
+    if code_length and as_numpy:
+        nats = nats.detach().to("cpu").numpy()
+    if loss is None:
+        return nats
+    if loss == "KL":
+        pred = student_t(loss, *fetch(obj), obj.p_nus)
+    else:
+        pred = fetch(obj)[0] if as_numpy else p_m
+    return (pred, nats) if code_length else pred

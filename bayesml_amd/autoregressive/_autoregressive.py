@@ -93,15 +93,29 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._device = device
         self._engine = None
         self._reg_pass_factory = None        # test seam only (tests/fake_regression_engine.py)
+        self._seq_engine = None
+        self._regseq_pass_factory = None     # test seam only (tests/regression_seq_oracle.py)
         ng.init_params(self, ("h0_", "hn_"), self.c_degree + 1)
         self.p_m = 0.0
         self.p_lambda = 0.5
         self.p_nu = 2.0
+        # what pred_and_update_sequence leaves: (p_ms, p_lambdas) as ndarrays, or device tensors fetched on first read
+        self._p = (np.zeros(1), np.full(1, 0.5))
+        self.p_nus = np.full(1, 2.0)
         self.set_h0_params(h0_mu_vec, h0_lambda_mat, h0_alpha, h0_beta)
 
+    @property
+    def p_ms(self):
+        return ng.fetch(self)[0]
+
+    @property
+    def p_lambdas(self):
+        return ng.fetch(self)[1]
+
     def __getstate__(self):
+        ng.fetch(self)
         state = dict(self.__dict__)
-        state["_engine"] = None
+        state["_engine"] = state["_seq_engine"] = None
         return state
 
     def get_constants(self):
@@ -125,9 +139,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.calc_pred_dist(np.zeros(self.c_degree))
         return self
 
-    def update_posterior(self, x, padding=None):
-        """Conjugate update over the lag windows (ref:477-504).  As in the reference, any ``padding`` other than
-        ``"zeros"`` means none: the first ``c_degree`` values only serve as initial values."""
+    def _check_series(self, x):
         if isinstance(x, torch.Tensor):
             if not (x.dtype.is_floating_point and x.dim() == 1):
                 raise DataFormatError("x must be a 1-dimensional numpy.ndarray.")
@@ -135,6 +147,11 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
             _check.float_vec(x, "x", DataFormatError)
         if x.shape[0] <= self.c_degree:
             raise DataFormatError("The length of x must greater than self.c_degree")
+
+    def update_posterior(self, x, padding=None):
+        """Conjugate update over the lag windows (ref:477-504).  As in the reference, any ``padding`` other than
+        ``"zeros"`` means none: the first ``c_degree`` values only serve as initial values."""
+        self._check_series(x)
         from .._regression import PAD_NONE, PAD_ZEROS
         eng = ng.data_pass(self, self.c_degree + 1)
         stats = eng.stats_window(eng.adopt(x), PAD_ZEROS if padding == "zeros" else PAD_NONE)
@@ -185,3 +202,34 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x)
         return prediction
+
+    def pred_and_update_sequence(self, x, padding=None, loss="squared", *, code_length=False, chunk_bytes=None):
+        """One-step-ahead prediction over the rows of ``update_posterior(x, padding)``, in order, in one device pass
+        (``_regseq.RegressionSeqPass``, DESIGN.md 4f "Sequential prediction"): value x[t] is predicted from its lag window
+        and the posterior of the windows before it, then learnt - ``pred_and_update(x[t - c_degree:t + 1], loss)`` for
+        t = c_degree .. len(x) - 1, or for every t with zeros at negative times when ``padding == "zeros"``.
+
+        ``x`` is accepted and refused as ``update_posterior`` does it (NumPy or torch, f32 or f64, a device tensor is read
+        where it lies); a refused sample changes nothing.  The return is the float64 ``[n]`` predictive means for ``loss``
+        "squared", "0-1" and "abs" - a NumPy array for NumPy input, a tensor on the model's device otherwise - and the
+        frozen ``scipy.stats.t`` over the n parameter arrays for "KL".  With ``code_length=True`` it is
+        ``(prediction, nats)``, ``nats[i] = -ln p(x[t_i] | earlier values)`` float64 ``[n]``; ``loss=None`` needs
+        ``code_length=True`` and returns ``nats`` alone.  Afterwards ``p_ms``, ``p_lambdas`` and ``p_nus`` hold the n
+        sequential parameter arrays, ``p_m``, ``p_lambda`` and ``p_nu`` the last position's, and ``hn_*`` are bit for bit
+        what ``update_posterior(x, padding)`` leaves: they come from that very pass over the series.  ``chunk_bytes``
+        bounds the workspace (default 256 MiB): the rows are cut into blocks, ``_regseq.plan_blocks(...)`` blocks go into
+        one pass, and the cut does not change a bit of the result."""
+        ng.check_sequence_loss(loss, code_length)
+        self._check_series(x)
+        from .._regression import PAD_NONE, PAD_ZEROS
+        as_numpy = not isinstance(x, torch.Tensor)
+        pad = PAD_ZEROS if padding == "zeros" else PAD_NONE
+        eng = ng.seq_pass(self, self.c_degree + 1)
+        xd = eng.adopt(x)
+        n = x.shape[0] - (0 if pad == PAD_ZEROS else self.c_degree)
+        out = ng.pred_and_update_sequence(
+            self, n, lambda start: eng.run_window(xd, pad, start, bool(code_length), chunk_bytes),
+            lambda: self.update_posterior(xd, padding), as_numpy, loss, code_length)
+        self.p_m, self.p_lambda = (np.float64(float(t[-1])) for t in self._p)
+        self.p_nu = float(self.p_nus[-1])
+        return out

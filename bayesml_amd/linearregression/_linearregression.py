@@ -96,6 +96,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._device = device
         self._engine = None
         self._reg_pass_factory = None        # test seam only (tests/fake_regression_engine.py)
+        self._seq_engine = None
+        self._regseq_pass_factory = None     # test seam only (tests/regression_seq_oracle.py)
         ng.init_params(self, ("h0_", "hn_"), self.c_degree)
         self._p = (np.zeros(1), np.ones(1))  # (p_ms, p_lambdas): ndarrays, or device tensors fetched on first read
         self.p_nus = np.full(1, 2.0)
@@ -104,9 +106,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
 
     # p_ms / p_lambdas are float64 ndarrays to the caller; after calc_pred_dist they live on the device until first read
     def _fetch(self):
-        if isinstance(self._p[0], torch.Tensor):
-            self._p = tuple(t.detach().to("cpu", torch.float64).numpy() for t in self._p)
-        return self._p
+        return ng.fetch(self)
 
     @property
     def p_ms(self):
@@ -119,7 +119,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def __getstate__(self):
         self._fetch()
         state = dict(self.__dict__)
-        state["_engine"] = None
+        state["_engine"] = state["_seq_engine"] = None
         return state
 
     def get_constants(self):
@@ -216,6 +216,29 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x, y)
         return prediction
+
+    def pred_and_update_sequence(self, x, y, loss="squared", *, code_length=False, chunk_bytes=None):
+        """``[pred_and_update(x[i], y[i], loss) for i in range(n)]`` over the rows of ``update_posterior(x, y)``, in order, in
+        one device pass (``_regseq.RegressionSeqPass``, DESIGN.md 4f "Sequential prediction"): prediction i is made from
+        the posterior of the rows before i, then row i is learnt.
+
+        ``x`` and ``y`` are accepted and refused as ``update_posterior`` does it (NumPy or torch, f32 or f64, a device
+        tensor is read where it lies); a refused sample changes nothing.  The return is the float64 ``[n]`` predictive
+        means for ``loss`` "squared", "0-1" and "abs" - a NumPy array for NumPy input, a tensor on the model's device
+        otherwise - and the frozen ``scipy.stats.t`` over the n parameter arrays for "KL".  With ``code_length=True`` it
+        is ``(prediction, nats)``, ``nats[i] = -ln p(y[i] | rows before i)`` float64 ``[n]``; ``loss=None`` needs
+        ``code_length=True`` and returns ``nats`` alone.  Afterwards ``p_ms``, ``p_lambdas`` and ``p_nus`` hold the n
+        sequential parameter arrays, and ``hn_*`` are bit for bit what ``update_posterior(x, y)`` leaves: they come from
+        that very pass over the sample.  ``chunk_bytes`` bounds the workspace (default 256 MiB): the rows are cut into
+        blocks, ``_regseq.plan_blocks(...)`` blocks go into one pass, and the cut does not change a bit of the result."""
+        ng.check_sequence_loss(loss, code_length)
+        as_numpy = not isinstance(x, torch.Tensor)
+        x, y = self._check_sample(x, y)
+        eng = ng.seq_pass(self, self.c_degree) if x.shape[0] > 0 else None
+        xd, yd = (eng.adopt(x), eng.adopt(y)) if eng is not None else (x, y)
+        return ng.pred_and_update_sequence(
+            self, x.shape[0], lambda start: eng.run(xd, yd, start, bool(code_length), chunk_bytes),
+            lambda: self.update_posterior(xd, yd), as_numpy, loss, code_length)
 
     def calc_log_marginal_likelihood(self):
         """ref:802-812."""
