@@ -24,7 +24,9 @@
 //         p_lambda = alpha_i / (beta_i s),  p_nu = 2 alpha_i,  p_m = y_i - R_ii v_i,
 //         nats = lnGamma(alpha_i) - lnGamma(alpha_i + 1/2) + ln(2 pi alpha_i / p_lambda) / 2 + (alpha_i + 1/2) log1p(v_i^2 / (2 beta_i)).
 //     Rows past the block's end are zero rows (K = I there) and write nothing.  A block that starts within the first 2 D
-//     rows of the call forms K and factorises it in double-double on the vector ALU instead (see "double-double" below).
+//     rows of the call, or whose binary64 K turns out to have a diagonal entry above kDdThreshold (a regressor that
+//     switches on late under a diffuse prior), forms K and factorises it in double-double on the vector ALU instead: the
+//     latter runs its slices a second time (see "double-double" below).
 // No atomics, no waiting on other workgroups, every sum in a fixed order.
 #pragma once
 #include "chol_blocked.h"
@@ -176,12 +178,18 @@ __device__ __attribute__((noinline)) double lgamma_half_step(double a) {
     return -(a * log1p(0.5 / a) + 0.5 * log(a) - 0.5 + (stirling_tail(a + 0.5) - stirling_tail(a)));
 }
 
-// ---- double-double, for the blocks of the first 2 D rows -------------------------------------------------------------------
+// ---- double-double, for the blocks that start from a nearly singular Lambda_c ----------------------------------------------
 // Until a call has seen 2 D rows, a block may start from a nearly singular Lambda_c (a diffuse prior): K = I + Z Z^T then
 // has entries of 1e6 and more whose Schur complements s_i are of order one, and every rounding of K or of its factor in
-// binary64 costs s_i that many digits, where the row loop refactorises Lambda and loses none.  Those few blocks form K and
-// factorise it in double-double on the vector ALU (error-free products by fma, Knuth's two-sum); the rounding of Z itself
-// is harmless, s_i being insensitive to relative perturbations of the rows of Z.
+// binary64 costs s_i that many digits, where the row loop refactorises Lambda and loses none.  Later blocks do the same
+// when a regressor that was zero so far switches on in them (a regime dummy, a level first seen at row 70): Lambda_c has
+// kept the prior's precision in that direction however many rows came before.  So a block forms K and factorises it in
+// double-double on the vector ALU (error-free products by fma, Knuth's two-sum) when it starts within the first 2 D rows,
+// or when a diagonal entry of its binary64 K exceeds kDdThreshold: K_ii = 1 + w_i^T Lambda_c^-1 w_i is 1 to 6 in every
+// block past 2 D rows of the tests' ordinary inputs and 1e6 in the onset blocks, and a block just below
+// the threshold loses at most that factor, six bits, in binary64.  The rounding of Z itself is harmless, s_i being
+// insensitive to relative perturbations of the rows of Z.
+constexpr double kDdThreshold = 64.0;
 struct dd {
     double hi, lo;
 };
@@ -291,60 +299,79 @@ __global__ __launch_bounds__(256) void block_innovations_kernel(SRC src, const i
     const bool valid = row < hi;
     const int64_t rowc = valid ? row : hi - 1;
     for (int e = tid; e < kBlock * kKLd; e += 256) km[e] = 0.0;
-    // a block of the first 2 D rows of the call: K and its factor in double-double (above), the thread's entries of the
-    // packed triangle being tid, tid + 256, ...
-    const bool head = mu[PD + 1] < 2.0 * D;          // (workgroup uniform)
+    // K and its factor in double-double (above): a block of the first 2 D rows of the call, or, decided after the binary64
+    // slices below, one whose K has a diagonal entry above kDdThreshold.  Workgroup uniform, and a function of the
+    // block's rows and start state alone.  The thread's entries of the packed triangle are tid, tid + 256, ...
+    bool head = mu[PD + 1] < 2.0 * D;
     dd kd[kTriPerThread];
     int ki[kTriPerThread], kj[kTriPerThread];
-#pragma unroll
-    for (int k = 0; k < kTriPerThread; ++k) {
-        ki[k] = kj[k] = 0;
-        kd[k] = dd{0.0, 0.0};
-        if (head) {
-            const int e = tid + 256 * k < kTriLen ? tid + 256 * k : kTriLen - 1;
-            int i = 0;
-            while (tri_at(i + 1, 0) <= e) ++i;
-            ki[k] = i;
-            kj[k] = e - tri_at(i, 0);
-            kd[k].hi = i == kj[k] ? 1.0 : 0.0;
-        }
-    }
     // the wave's lower tiles of K: numbers wv, wv + 4, wv + 8 of (0,0) (1,0) (1,1) (2,0) ... (3,3)
     d4 kacc[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) kacc[k] = d4{0.0, 0.0, 0.0, 0.0};
-    double dot = 0.0;
-    for (int s = 0; s < nt; ++s) {
-        d4 z = d4{0.0, 0.0, 0.0, 0.0};
-        for (int jt = 0; jt <= s; ++jt) {
+    double dot;
+    for (;;) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int f = 16 * jt + 4 * p + lg;                         // (f < PD <= 16 T: the sources clamp it)
-                const double a = valid ? src.value(rowc, f, src.raw(rowc, f)) : 0.0;
-                z = mfma_f64(a, mat[(16 * s + li) * PD + f], z);
-                if (s == nt - 1) dot = fma(a, mu[f], dot);
+        for (int k = 0; k < kTriPerThread; ++k) {
+            ki[k] = kj[k] = 0;
+            kd[k] = dd{0.0, 0.0};
+            if (head) {
+                const int e = tid + 256 * k < kTriLen ? tid + 256 * k : kTriLen - 1;
+                int i = 0;
+                while (tri_at(i + 1, 0) <= e) ++i;
+                ki[k] = i;
+                kj[k] = e - tri_at(i, 0);
+                kd[k].hi = i == kj[k] ? 1.0 : 0.0;
             }
         }
-        double* buf = zs + (s & 1) * (kBlock * kZLd);
+        dot = 0.0;
+        for (int s = 0; s < nt; ++s) {
+            d4 z = d4{0.0, 0.0, 0.0, 0.0};
+            for (int jt = 0; jt <= s; ++jt) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) buf[(16 * wv + lg + 4 * r) * kZLd + li] = z[r];
-        __syncthreads();           // (buffer s & 1 is written again at s + 2, behind the barrier of s + 1)
-        if (head) {
+                for (int p = 0; p < 4; ++p) {
+                    const int f = 16 * jt + 4 * p + lg;                         // (f < PD <= 16 T: the sources clamp it)
+                    const double a = valid ? src.value(rowc, f, src.raw(rowc, f)) : 0.0;
+                    z = mfma_f64(a, mat[(16 * s + li) * PD + f], z);
+                    if (s == nt - 1) dot = fma(a, mu[f], dot);
+                }
+            }
+            double* buf = zs + (s & 1) * (kBlock * kZLd);
 #pragma unroll
-            for (int k = 0; k < kTriPerThread; ++k)
-                for (int c = 0; c < 16; ++c) kd[k] = dd_add(kd[k], dd_two_prod(buf[ki[k] * kZLd + c], buf[kj[k] * kZLd + c]));
-            continue;
+            for (int r = 0; r < 4; ++r) buf[(16 * wv + lg + 4 * r) * kZLd + li] = z[r];
+            __syncthreads();           // (buffer s & 1 is written again at s + 2, behind the barrier of s + 1)
+            if (head) {
+#pragma unroll
+                for (int k = 0; k < kTriPerThread; ++k)
+                    for (int c = 0; c < 16; ++c) kd[k] = dd_add(kd[k], dd_two_prod(buf[ki[k] * kZLd + c], buf[kj[k] * kZLd + c]));
+                continue;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int t = wv + 4 * k;
+                if (t < 10) {
+                    const int rt = t >= 6 ? 3 : (t >= 3 ? 2 : (t >= 1 ? 1 : 0)), ct = t - rt * (rt + 1) / 2;
+#pragma unroll
+                    for (int p = 0; p < 4; ++p)
+                        kacc[k] = mfma_f64(buf[(16 * rt + li) * kZLd + 4 * p + lg], buf[(16 * ct + li) * kZLd + 4 * p + lg], kacc[k]);
+                }
+            }
         }
+        if (head) break;
+        // the largest diagonal entry of the binary64 K (its diagonal tiles are numbers 0, 2, 5, 9): above the threshold the
+        // slices run again in double-double; below it nothing of the block's arithmetic has changed
+        bool large = false;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int t = wv + 4 * k;
-            if (t < 10) {
-                const int rt = t >= 6 ? 3 : (t >= 3 ? 2 : (t >= 1 ? 1 : 0)), ct = t - rt * (rt + 1) / 2;
+            if (t == 0 || t == 2 || t == 5 || t == 9) {
 #pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    kacc[k] = mfma_f64(buf[(16 * rt + li) * kZLd + 4 * p + lg], buf[(16 * ct + li) * kZLd + 4 * p + lg], kacc[k]);
+                for (int r = 0; r < 4; ++r)
+                    if (lg + 4 * r == li) large = large || kacc[k][r] + 1.0 > kDdThreshold;
             }
         }
+        if (!__syncthreads_or(large)) break;
+        head = true;
     }
     __syncthreads();               // km is zero everywhere
     if (head) {

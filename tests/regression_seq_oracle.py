@@ -2,13 +2,15 @@
 
 * ``block_form``: a NumPy restatement of the block form of DESIGN.md 4f "Sequential prediction" with the kernels' schedule
   (``schedule``, restated here, not imported) and their order of operations: per-block statistics, an exclusive scan in
-  block order from a carry, the block-start state from the prefix, the block's marginal factor.
+  block order from a carry, the block-start state from the prefix, the block's marginal factor - in double-double
+  (``dd_block_factor``) for the blocks the kernels take there: the first 2 D rows, and K_ii above ``DD_THRESHOLD``.
 * ``row_loop``: the row-by-row loop from ``regression_oracle.update`` / ``pred_params`` (the reference's formulas in float64).
 * ``ld_row_loop``: the same loop in ``numpy.longdouble`` with a plain Cholesky (restated from
   tests/golden/make_golden_regression.py): the "exact" value the tests compare against.
 * ``CpuRegressionSeqPass``: CPU stand-in for ``bayesml_amd._regseq.RegressionSeqPass`` behind the private
   ``LearnModel._regseq_pass_factory`` seam; the product path never constructs it.
 * ``errors`` / ``tolerance``: the measure and the bound every comparison uses.
+* ``sweep`` and the small model helpers of the GPU tests.
 """
 import numpy as np
 import torch
@@ -78,9 +80,86 @@ def start_state(mu, lam, alpha, beta):
     return np.concatenate([lam.reshape(-1), lm, [mu @ lm, float(alpha), float(beta)]])
 
 
-def block_form(w, y, start, blocks_per_pass=None):
+DD_THRESHOLD = 64.0        # csrc/regseq_kernels.h: kDdThreshold ("Double-double")
+
+
+# ---- double-double, as csrc/regseq_kernels.h has it (a number is the pair hi, lo of float64 arrays) ---------------------
+# (long double is not enough for K: its entries reach 1e6 and more where the Schur complements are of order one, and 64
+# mantissa bits leave those 1e-13 off - the row loop in float64 has 1e-15)
+def _dd_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _dd_add(a, b):
+    hi, lo = _dd_sum(a[0], b[0])
+    lo = lo + (a[1] + b[1])
+    h = hi + lo
+    return h, lo - (h - hi)
+
+
+def _two_prod(a, b):
+    """a b exactly (Veltkamp's split and Dekker's product, where the kernel has an fma)."""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _dd_mul(a, b):
+    p, e = _two_prod(a[0], b[0])
+    e = e + (a[0] * b[1] + a[1] * b[0])
+    h = p + e
+    return h, e - (h - p)
+
+
+def _dd_neg(a):
+    return -a[0], -a[1]
+
+
+def _dd_div(a, b):
+    zero = np.zeros_like(b[0])
+    q1 = a[0] / b[0]
+    r = _dd_add(a, _dd_neg(_dd_mul((q1, zero), b)))
+    q2 = r[0] / b[0]
+    r = _dd_add(r, _dd_neg(_dd_mul((q2, zero), b)))
+    q3 = r[0] / b[0]
+    return _dd_add(_dd_sum(q1, q2), (q3, zero))
+
+
+def _dd_sqrt(a):
+    x = np.sqrt(a[0])
+    zero = np.zeros_like(x)
+    r = _dd_add(a, _dd_neg(_dd_mul((x, zero), (x, zero))))
+    return _dd_sum(x, r[0] / (2.0 * x))
+
+
+def dd_block_factor(z):
+    """The factor R of K = I + z z^T as the kernel's double-double path forms it: K summed column of z by column of z from
+    error-free products, then the right-looking Cholesky of ``dd_cholesky_packed``; the high words of R."""
+    z = np.asarray(z, dtype=np.float64)
+    m = z.shape[0]
+    k = (np.eye(m), np.zeros((m, m)))
+    for c in range(z.shape[1]):
+        k = _dd_add(k, _two_prod(z[:, c, None], z[None, :, c]))
+    hi, lo = k
+    for j in range(m):
+        d = _dd_sqrt((hi[j, j], lo[j, j]))
+        col = _dd_div((hi[j + 1:, j], lo[j + 1:, j]), (np.full(m - j - 1, d[0]), np.full(m - j - 1, d[1])))
+        hi[j, j], lo[j, j] = d
+        hi[j + 1:, j], lo[j + 1:, j] = col
+        upd = _dd_mul((-col[0][:, None], -col[1][:, None]), (col[0][None, :], col[1][None, :]))
+        hi[j + 1:, j + 1:], lo[j + 1:, j + 1:] = _dd_add((hi[j + 1:, j + 1:], lo[j + 1:, j + 1:]), upd)
+    return np.tril(hi)
+
+
+def block_form(w, y, start, blocks_per_pass=None, dd_threshold=DD_THRESHOLD, diag=None):
     """(p_ms, p_lambdas, p_nus, nats) of the rows w [n, D], targets y [n], from the state ``start`` (``start_state``).
-    ``blocks_per_pass``: cut the call into passes of so many blocks, carrying [G | c | s | n] between them."""
+    ``blocks_per_pass``: cut the call into passes of so many blocks, carrying [G | c | s | n] between them.
+    ``dd_threshold``: None takes the data out of the double-double decision (the form before the criterion existed).
+    ``diag``: a list that receives (first row, end, starts within the first 2 D rows, max_i K_ii) of every block."""
     from scipy.linalg import solve_triangular
     w, y = np.asarray(w, dtype=np.float64), np.asarray(y, dtype=np.float64)
     n, D = w.shape
@@ -109,11 +188,16 @@ def block_form(w, y, start, blocks_per_pass=None):
             beta_c = beta0 + ((s + m0) - u @ u) / 2.0
             lo, hi = bounds[b], bounds[b + 1]                            # (4) the block's innovations
             z = w[lo:hi] @ linv.T
-            if rows_before < 2 * D:      # the first 2 D rows: K and its factor in extended precision (the kernel: double-double)
-                zl = z.astype(LD)
-                r = ld_cholesky(np.eye(hi - lo, dtype=LD) + zl @ zl.T).astype(np.float64)
+            k = np.eye(hi - lo) + z @ z.T
+            k_max = float(np.max(np.diag(k)))
+            if diag is not None:
+                diag.append((lo, hi, rows_before < 2 * D, k_max))
+            # K and its factor in double-double for a block of the first 2 D rows, and for one whose binary64 K has a
+            # diagonal entry above the threshold: a function of the block's rows and start state
+            if rows_before < 2 * D or (dd_threshold is not None and k_max > dd_threshold):
+                r = dd_block_factor(z)
             else:
-                r = np.linalg.cholesky(np.eye(hi - lo) + z @ z.T)
+                r = np.linalg.cholesky(k)
             v = solve_triangular(r, y[lo:hi] - w[lo:hi] @ mu_c, lower=True)
             v2 = v * v
             before = np.concatenate([[0.0], np.cumsum(v2)[:-1]])
@@ -161,9 +245,10 @@ def ld_forward(low, b):
     return z
 
 
-def ld_row_loop(w, y, mu, lam, alpha, beta):
+def ld_row_loop(w, y, mu, lam, alpha, beta, rows=None):
     """The loop in long double, as statistics (the state before row i is a function of the sums over the rows before it, so
-    nothing accumulates but those sums): (p_ms, p_lambdas, p_nus, nats)."""
+    nothing accumulates but those sums): (p_ms, p_lambdas, p_nus, nats).  ``rows``: the rows to predict (all of them if
+    None); the sums run over every row, the factorisation only at those, and the other rows' outputs are NaN."""
     w, y = np.asarray(w, dtype=np.float64).astype(LD), np.asarray(y, dtype=np.float64).astype(LD)
     n, D = w.shape
     lam0, mu0 = np.array(lam, dtype=LD), np.array(mu, dtype=LD)
@@ -171,21 +256,29 @@ def ld_row_loop(w, y, mu, lam, alpha, beta):
     lm0, m0 = lam0 @ mu0, mu0 @ lam0 @ mu0
     g, c, s = np.zeros((D, D), dtype=LD), np.zeros(D, dtype=LD), LD(0)
     out = [np.zeros(n, dtype=LD) for _ in range(4)]
+    wanted = np.ones(n, dtype=bool)
+    if rows is not None:
+        wanted[:] = False
+        wanted[np.asarray(rows, dtype=np.int64)] = True
+        for o in out:
+            o[~wanted] = np.nan
     for i in range(n):
-        low = ld_cholesky(lam0 + g)
-        u = ld_forward(low, lm0 + c)
-        q = ld_forward(low, w[i])
-        a_i = alpha0 + LD(i) / 2
-        b_i = beta0 + (s + m0 - u @ u) / 2
-        out[0][i] = q @ u                                   # w . mu = (L^-1 w) . (L^-1 r)
-        out[1][i] = a_i / b_i / (1 + q @ q)
-        out[2][i] = 2 * a_i
+        if wanted[i]:
+            low = ld_cholesky(lam0 + g)
+            u = ld_forward(low, lm0 + c)
+            q = ld_forward(low, w[i])
+            a_i = alpha0 + LD(i) / 2
+            b_i = beta0 + (s + m0 - u @ u) / 2
+            out[0][i] = q @ u                               # w . mu = (L^-1 w) . (L^-1 r)
+            out[1][i] = a_i / b_i / (1 + q @ q)
+            out[2][i] = 2 * a_i
         g += np.outer(w[i], w[i])
         c += w[i] * y[i]
         s += y[i] * y[i]
-    e2 = out[1] * (y - out[0]) ** 2 / out[2]
-    half = out[2] / 2
-    out[3] = (ld_lgamma_half_step(half) + np.log(2 * LD(np.pi) * half / out[1]) / 2 + (half + LD(0.5)) * np.log1p(e2))
+    e2 = out[1][wanted] * (y[wanted] - out[0][wanted]) ** 2 / out[2][wanted]
+    half = out[2][wanted] / 2
+    out[3][wanted] = (ld_lgamma_half_step(half) + np.log(2 * LD(np.pi) * half / out[1][wanted]) / 2
+                      + (half + LD(0.5)) * np.log1p(e2))
     return tuple(out)
 
 
@@ -214,11 +307,16 @@ def tolerance(ref_err):
     return {k: max(8.0 * v, 64.0 * EPS) for k, v in ref_err.items()}
 
 
-def check(label, got, exact, ref, y, D):
+def check(label, got, exact, ref, y, D, rows=None):
     """Holds ``got`` to the bound, separately on the first 2 D rows and on the rest; prints worst error / tolerance.
-    ``ref``: the reference loop's outputs on the same rows, or a dict {"head": errors, "rest": errors} recorded earlier."""
+    ``ref``: the reference loop's outputs on the same rows, or a dict {"head": errors, "rest": errors} recorded earlier.
+    ``rows``: the row numbers to compare (``ld_row_loop``'s ``rows``), all of them if None."""
     worst = 0.0
-    for part, rows in (("head", slice(0, 2 * D)), ("rest", slice(2 * D, None))):
+    parts = (slice(0, 2 * D), slice(2 * D, None))
+    if rows is not None:
+        rows = np.asarray(rows, dtype=np.int64)
+        parts = (rows[rows < 2 * D], rows[rows >= 2 * D])
+    for part, rows in zip(("head", "rest"), parts):
         ref_err = ref[part] if isinstance(ref, dict) else errors(ref, exact, y, rows)
         tol, err = tolerance(ref_err), errors(got, exact, y, rows)
         ratios = {k: err[k] / tol[k] for k in err}
@@ -293,3 +391,58 @@ def model_of(g, start, real=False):
         m, args = lr.LearnModel(int(g["D"])), (g["x"], g["y"])
     m.set_hn_params(*start)
     return (m if real else stand_ins(m)), args
+
+
+# ---- the models on the device (the GPU tests' helpers) ----------------------------------------------------------------------
+DEFAULT = lambda D: (np.zeros(D), np.eye(D), 1.0, 1.0)      # noqa: E731
+HN = ("hn_mu_vec", "hn_lambda_mat", "hn_alpha", "hn_beta")
+
+
+def dev():
+    return torch.device("cuda", 0)
+
+
+def linreg(D, start=None):
+    from bayesml_amd import linearregression as lr
+    m = lr.LearnModel(D, device=dev())
+    return m if start is None else m.set_hn_params(*start)
+
+
+def autoreg(p, start=None):
+    from bayesml_amd import autoregressive as ar
+    m = ar.LearnModel(p, device=dev())
+    return m if start is None else m.set_hn_params(*start)
+
+
+def hn_equal(a, b):
+    return all(np.array_equal(getattr(a, k), getattr(b, k)) for k in HN)
+
+
+def synth(D, n, seed, intercept=0.0):
+    x, y, _ = orc.synth_linreg(D, n, seed, 2.0, np.float64)
+    return x, y + intercept
+
+
+def budget_for(D, blocks):
+    """chunk_bytes that makes a pass hold so many blocks."""
+    from bayesml_amd import _regseq
+    return 8 * _regseq.work_slots(D, blocks)
+
+
+def sweep(label, make, rows_of, ns, w, y, start, rows=None):
+    """Every n of ``ns`` is a call on the first n rows; the loops run once, on the longest: prediction i does not depend on
+    the rows after i.  ``rows``: the rows the long-double loop predicts and the comparison looks at (all if None)."""
+    D = w.shape[1]
+    exact = ld_row_loop(w, y, *start, rows=rows)
+    ref = row_loop(w, y, *start)[:4]
+    worst = 0.0
+    for n in ns:
+        m = make()
+        pred, nats = m.pred_and_update_sequence(*rows_of(n), code_length=True)
+        got = (pred, m.p_lambdas, m.p_nus, nats)
+        assert all(a.shape == (n,) for a in got)
+        sub = None if rows is None else [i for i in rows if i < n]
+        worst = max(worst, check(f"{label} n = {n}", got, [e[:n] for e in exact], [r[:n] for r in ref], y[:n], D, rows=sub))
+        assert hn_equal(m, make().update_posterior(*rows_of(n)))
+    print(f"{label}: worst error / tolerance {worst:.2f}")
+    return worst

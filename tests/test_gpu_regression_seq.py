@@ -19,32 +19,8 @@ pytestmark = pytest.mark.gpu
 
 B = seq.BLOCK
 NS = (1, B - 1, B, B + 1, 3 * B + 17)
-DEFAULT = lambda D: (np.zeros(D), np.eye(D), 1.0, 1.0)      # noqa: E731
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def linreg(D, start=None):
-    from bayesml_amd import linearregression as lr
-    m = lr.LearnModel(D, device=dev())
-    return m if start is None else m.set_hn_params(*start)
-
-
-def autoreg(p, start=None):
-    from bayesml_amd import autoregressive as ar
-    m = ar.LearnModel(p, device=dev())
-    return m if start is None else m.set_hn_params(*start)
-
-
-def hn_equal(a, b):
-    return all(np.array_equal(getattr(a, k), getattr(b, k)) for k in ("hn_mu_vec", "hn_lambda_mat", "hn_alpha", "hn_beta"))
-
-
-def synth(D, n, seed, intercept=0.0):
-    x, y, _ = orc.synth_linreg(D, n, seed, 2.0, np.float64)
-    return x, y + intercept
+DEFAULT, dev, linreg, autoreg, hn_equal, synth, sweep = (seq.DEFAULT, seq.dev, seq.linreg, seq.autoreg, seq.hn_equal, seq.synth,
+                                                         seq.sweep)
 
 
 @pytest.mark.parametrize("name", seq.FIXTURES)
@@ -61,23 +37,6 @@ def test_fixtures(name):
     assert hn_equal(m, u.update_posterior(*args))
     if "p" in g:
         assert (m.p_m, m.p_lambda, m.p_nu) == (m.p_ms[-1], m.p_lambdas[-1], m.p_nus[-1])
-
-
-def sweep(label, make, rows_of, ns, w, y, start):
-    """Every n of ``ns`` is a call on the first n rows; the loops run once, on the longest: prediction i does not depend on
-    the rows after i."""
-    D = w.shape[1]
-    exact = seq.ld_row_loop(w, y, *start)
-    ref = seq.row_loop(w, y, *start)[:4]
-    worst = 0.0
-    for n in ns:
-        m = make()
-        pred, nats = m.pred_and_update_sequence(*rows_of(n), code_length=True)
-        got = (pred, m.p_lambdas, m.p_nus, nats)
-        assert all(a.shape == (n,) for a in got)
-        worst = max(worst, seq.check(f"{label} n = {n}", got, [e[:n] for e in exact], [r[:n] for r in ref], y[:n], D))
-        assert hn_equal(m, make().update_posterior(*rows_of(n)))
-    print(f"{label}: worst error / tolerance {worst:.2f}")
 
 
 @pytest.mark.parametrize("D", (1, 2, 15, 16, 17, 33, 128, 256))
@@ -110,9 +69,7 @@ def test_hard_priors_and_targets(case):
     sweep(case, lambda: linreg(D, start), lambda k: (x[:k], y[:k]), (n,), x, y, start)
 
 
-def budget_for(D, blocks):
-    from bayesml_amd import _regseq
-    return 8 * _regseq.work_slots(D, blocks)
+budget_for = seq.budget_for
 
 
 @pytest.mark.parametrize("kind", ("linreg", "ar"))

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import regression_oracle as orc
+import regression_seq_cases as cases
 import regression_seq_oracle as seq
 from conftest import ROOT, load_golden
 
@@ -33,6 +34,48 @@ def test_block_form_against_the_reference_fixtures(name):
     w, y, start, exact, ref = seq.fixture_parts(g)
     got = seq.block_form(w, y, seq.start_state(*start))
     print("worst error / tolerance: %.2f" % seq.check(name, got, exact, ref, y, w.shape[1]))
+
+
+def test_no_fixture_block_is_flagged_by_its_data():
+    """Past the first 2 D rows max_i K_ii of every fixture's blocks is far below the double-double threshold (measured:
+    2.9 at most, regression_seq_linreg_d3_default), so the criterion leaves their bits alone."""
+    worst = 0.0
+    for name in seq.FIXTURES:
+        w, y, start, _exact, _ref = seq.fixture_parts(load_golden(name))
+        diag = []
+        got = seq.block_form(w, y, seq.start_state(*start), diag=diag)
+        worst = max([worst] + [k for _lo, _hi, head, k in diag if not head])
+        for a, b in zip(got, seq.block_form(w, y, seq.start_state(*start), dd_threshold=None)):
+            assert np.array_equal(a, b), name
+    print(f"largest K_ii past the first 2 D rows: {worst:.2f}")
+    assert worst <= seq.DD_THRESHOLD / 8
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_block_form_on_late_features(name):
+    """A regressor that switches on late (regression_seq_cases.py), at the bound of the module docstring against the
+    float64 row loop.  Measured here, worst error / tolerance: late column 0.18, late dummy 0.16, control 0.09 (all on the
+    first 2 D rows; 0.08 and below on the rest).  With the data out of the double-double decision the two diffuse cases
+    miss the bound on the rest by factors of 1012 (p_m), 3004 (p_lambda), 1344 (nats) and 13464, 1416, 1400: the onset block
+    [63, 127) has K_ii of 4.7e6 and 1.0e6, every other block past 2 D rows 2.1 at most; the control's has 5.7 and its bits
+    do not depend on the criterion."""
+    c = cases.make(name)
+    assert c.onset_block == slice(63, 127) and not c.x[:c.onset, 3 if c.onset == 100 else 2].any()
+    exact = seq.ld_row_loop(c.x, c.y, *c.start)
+    ref = seq.row_loop(c.x, c.y, *c.start)[:4]
+    diag = []
+    got = seq.block_form(c.x, c.y, seq.start_state(*c.start), diag=diag)
+    print("worst error / tolerance: %.2f" % seq.check(name, got, exact, ref, c.y, cases.D))
+    flagged = [(lo, hi) for lo, hi, head, k in diag if not head and k > seq.DD_THRESHOLD]
+    old = seq.block_form(c.x, c.y, seq.start_state(*c.start), dd_threshold=None)
+    if name == "control":
+        assert flagged == [] and all(np.array_equal(a, b) for a, b in zip(got, old))
+        return
+    assert flagged == [(63, 127)]
+    with pytest.raises(AssertionError):
+        seq.check(name + " (rows alone decide)", old, exact, ref, c.y, cases.D)
+    rows = np.r_[0:63, 127:cases.N]
+    assert all(np.array_equal(a[rows], b[rows]) for a, b in zip(got, old))       # (the other blocks keep their bits)
 
 
 @pytest.mark.parametrize("per_pass", (1, 2, 7))
