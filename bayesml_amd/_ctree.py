@@ -58,7 +58,35 @@ def offsets(k: int, D: int):
     return off
 
 
-class CtreePass:
+class PassBase:
+    """What ``CtreePass`` and ``_ctsp.SparseCtreePass`` spell alike: nothing here depends on how a level's table is laid
+    out, only on ``device``, ``D``, ``off`` (level D is the last) and the tensors ``g``, ``beta`` and ``exists``."""
+
+    def adopt(self, x):
+        return adopt_tensor(x, self.device, "i")
+
+    def any_negative(self, x) -> bool:
+        return bool((x < 0).any()) if x.dtype != torch.uint8 else False
+
+    def _head(self, x):
+        """The first min(n, D) symbols as int32, and their number: the samples that end above the maximal depth."""
+        n_head = min(int(x.shape[0]), self.D)
+        return x[:n_head].to(torch.int32), n_head
+
+    def fill_existing(self, g=None, beta=None):
+        """What the reference's ``_set_hn_g_recursion`` / ``_set_hn_beta_vec_recursion`` do: every existing node gets the
+        value (g = 0 at the maximal depth)."""
+        m = self.exists != 0
+        if g is not None:
+            oD = self.off[self.D]
+            self.g[:oD] = torch.where(m[:oD], float(g), self.g[:oD])
+            self.g[oD:] = torch.where(m[oD:], 0.0, self.g[oD:])
+        if beta is not None:
+            b = torch.as_tensor(np.asarray(beta, dtype=np.float64), device=self.device)
+            self.beta.copy_(torch.where(m[:, None], b[None, :], self.beta))
+
+
+class CtreePass(PassBase):
     """The tables of one context tree on one device and the three entry points on them."""
 
     def __init__(self, k: int, D: int, device=None):
@@ -78,12 +106,6 @@ class CtreePass:
         self.launch_info = ""
 
     # ---- the sample -----------------------------------------------------------------------------------------------------
-    def adopt(self, x):
-        return adopt_tensor(x, self.device, "i")
-
-    def any_negative(self, x) -> bool:
-        return bool((x < 0).any()) if x.dtype != torch.uint8 else False
-
     def count(self, x: torch.Tensor) -> torch.Tensor:
         """``[n | bad | cnt_D[k^D][k]]`` of the adopted sample, int64 on the device (overwritten by the next call)."""
         with torch.cuda.device(self.device):
@@ -96,8 +118,7 @@ class CtreePass:
     def sweep(self, x: torch.Tensor, hn_g: float, hn_beta_vec, want_counts=False):
         """The up-sweep on the counts of the last ``count(x)``.  With ``want_counts`` the counts of levels 0..D-1 are
         returned as an int64 tensor [nodes of those levels, k]."""
-        n_head = min(int(x.shape[0]), self.D)
-        head = x[:n_head].to(torch.int32)
+        head, n_head = self._head(x)
         hb = torch.as_tensor(np.asarray(hn_beta_vec, dtype=np.float64), device=self.device)
         cl = torch.zeros(self.off[self.D], self.k, dtype=torch.int64, device=self.device) if want_counts else None
         with torch.cuda.device(self.device):
@@ -139,18 +160,6 @@ class CtreePass:
     def clear(self):
         self.exists.zero_()
         self.leaf.zero_()
-
-    def fill_existing(self, g=None, beta=None):
-        """What the reference's ``_set_hn_g_recursion`` / ``_set_hn_beta_vec_recursion`` do: every existing node gets the
-        value (g = 0 at the maximal depth)."""
-        m = self.exists != 0
-        if g is not None:
-            oD = self.off[self.D]
-            self.g[:oD] = torch.where(m[:oD], float(g), self.g[:oD])
-            self.g[oD:] = torch.where(m[oD:], 0.0, self.g[oD:])
-        if beta is not None:
-            b = torch.as_tensor(np.asarray(beta, dtype=np.float64), device=self.device)
-            self.beta.copy_(torch.where(m[:, None], b[None, :], self.beta))
 
     def gather(self, idx):
         """The rows ``idx`` (a short list of table indices: one path) as host arrays g, beta, exists, leaf."""

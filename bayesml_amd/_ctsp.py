@@ -17,8 +17,8 @@ import ctypes
 import numpy as np
 import torch
 
+from ._ctree import PassBase
 from ._engine import EngineError, EngineLimitError
-from ._expfam import adopt_tensor
 from ._native import bind, gpu_device, stream_ptr
 
 U8, I32, I64 = range(3)                  # enum ctsp_dtype
@@ -91,7 +91,7 @@ def child_key(key: int, level: int, c: int, k: int, D: int) -> int:
     return int(key) | (int(c) << (symbol_bits(k) * (D - level - 1)))
 
 
-class SparseCtreePass:
+class SparseCtreePass(PassBase):
     """The hash tables of one context tree on one device and the entry points on them.
 
     ``budget_bytes``: the most the tables may take (``EngineLimitError`` beyond, state untouched).  ``floor_capacity``: the
@@ -195,16 +195,6 @@ class SparseCtreePass:
             self._recount()             # (a rehash drops the slots that were claimed for a refused sample)
 
     # ---- the sample -------------------------------------------------------------------------------------------------------
-    def adopt(self, x):
-        return adopt_tensor(x, self.device, "i")
-
-    def any_negative(self, x) -> bool:
-        return bool((x < 0).any()) if x.dtype != torch.uint8 else False
-
-    def _head(self, x):
-        n_head = min(int(x.shape[0]), self.D)
-        return x[:n_head].to(torch.int32), n_head
-
     def count(self, x: torch.Tensor):
         """Zero the scratch and count the deepest level (enqueue only; the caller has reserved room)."""
         with torch.cuda.device(self.device):
@@ -331,17 +321,6 @@ class SparseCtreePass:
         self.exists.zero_()
         self.leaf.zero_()
         self._used = [0] * (self.D + 1)
-
-    def fill_existing(self, g=None, beta=None):
-        """Every node gets the value (g = 0 at the maximal depth), as ``CtreePass.fill_existing``."""
-        m = self.exists != 0
-        if g is not None:
-            oD = self.off[self.D]
-            self.g[:oD] = torch.where(m[:oD], float(g), self.g[:oD])
-            self.g[oD:] = torch.where(m[oD:], 0.0, self.g[oD:])
-        if beta is not None:
-            b = torch.as_tensor(np.asarray(beta, dtype=np.float64), device=self.device)
-            self.beta.copy_(torch.where(m[:, None], b[None, :], self.beta))
 
     def close(self):
         self.key = self.beta = self.g = self.exists = self.leaf = self._cnt = self._lnw = None

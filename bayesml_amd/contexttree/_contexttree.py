@@ -11,20 +11,18 @@ loop of ``pred_and_update`` over a whole sample in its level-wise form (``_ctseq
 materialises the ``_Node`` tree from the tables on demand; a tree given to a setter is scattered into them.
 
 With ``tables="sparse"`` the posterior lives in per-level hash tables that hold only the nodes that exist
-(``_ctsp.SparseCtreePass``, the same update by the ``ctsp_*`` entry points); nodes are then addressed by (level, key), and
-that index arithmetic is in ``_sparse``.
+(``_ctsp.SparseCtreePass``, the same update by the ``ctsp_*`` entry points).  What differs between the two storages on the
+host is a store of ``_nodes``, chosen at construction; the tree algorithms are written once there, on (level, key).
 
 ``GenModel`` is host NumPy: the chain is sequential and short.
 """
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
 
-from .. import _check, _ctree, _ctseq, _ctsp, base
-from . import _sparse
-from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
+from .. import _check, _ctree, _ctseq, base
+from . import _nodes
+from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError
 
 _INT_VEC_MSG = " must be a 1-dimensional numpy.ndarray whose dtype is int. Its values must be non-negative (including 0)."
 
@@ -221,12 +219,12 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if tables not in ("dense", "sparse"):
             raise ParameterFormatError("tables must be \"dense\" or \"sparse\"")
         self._sparse = tables == "sparse"
-        (_ctsp if self._sparse else _ctree).check_limit(self.c_k, self.c_d_max)
+        self._store = _nodes.store_for(self._sparse, self.c_k, self.c_d_max)
         self._device = device
         self._engine = None
         self._saved_tables = None
         self._has_root = False
-        self._off = None if self._sparse else _ctree.offsets(self.c_k, self.c_d_max)
+        self._off = self._store.off
 
         self.h0_g = h0_g
         self.h0_beta_vec = np.ones(self.c_k) / 2
@@ -238,34 +236,30 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
 
     # ---- the engine and its tables ---------------------------------------------------------------------------------------
     def _eng(self):
-        if self._engine is None and self._sparse:
-            self._engine = _sparse.make_engine(self)
-            if self._saved_tables is not None:
-                self._engine.set_nodes(self._saved_tables)
-                self._saved_tables = None
         if self._engine is None:
-            make = self._ctree_pass_factory
-            self._engine = (make(self.c_k, self.c_d_max) if make is not None
-                            else _ctree.CtreePass(self.c_k, self.c_d_max, self._device))
+            self._engine = self._store.make_engine(self)
             if self._saved_tables is not None:
-                self._engine.set_tables(self._saved_tables)
+                self._store.restore(self._engine, self._saved_tables)
                 self._saved_tables = None
         return self._engine
 
     def __getstate__(self):
         state = dict(self.__dict__)
         if self._engine is not None and self._has_root:
-            state["_saved_tables"] = self._engine.get_nodes() if self._sparse else self._engine.get_tables()
+            state["_saved_tables"] = self._store.save(self._engine)
         state["_engine"] = None
         state.pop("_seq_pass", None)
+        state.pop("_store", None)           # (derived on loading: the state keeps the layout it always had)
         return state
+
+    def __getattr__(self, name):
+        if name != "_store":
+            raise AttributeError(name)
+        self._store = _nodes.store_for(self._sparse, self.c_k, self.c_d_max)      # (a model restored from a pickled state)
+        return self._store
 
     def get_constants(self):
         return {"c_k": self.c_k, "c_d_max": self.c_d_max}
-
-    def _root_index(self):
-        """The root as the engine addresses it: table index 0, or (level, key) = (0, 0)."""
-        return (0, 0) if self._sparse else 0
 
     def _default_g(self, depth):
         return 0.0 if depth == self.c_d_max else self.hn_g
@@ -276,50 +270,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         or ``None`` before the first update."""
         if not self._has_root:
             return None
-        if self._sparse:
-            return _sparse.hn_root(self, _Node)
-        t = self._eng().get_tables()
-        k, off, level = self.c_k, self._off, {}
-        for d in range(self.c_d_max + 1):
-            below = level
-            level = {}
-            for s in np.flatnonzero(t["exists"][off[d]:off[d + 1]]):
-                s = int(s)
-                node = _Node(d, k, float(t["g"][off[d] + s]))
-                node.h_beta_vec[:] = t["beta"][off[d] + s]
-                node.leaf = bool(t["leaf"][off[d] + s])
-                level[s] = node
-                if d > 0:
-                    below[s % k ** (d - 1)].children[s // k ** (d - 1)] = node
-            if d == 0:
-                root = level[0]
-        return root
-
-    def _scatter_tree(self, t, d, s, orig):
-        """ref:547-576 on the tables ``t`` (host copies): superpose ``orig`` on the existing node s of level d."""
-        k, D, off = self.c_k, self.c_d_max, self._off
-        i = off[d] + s
-        if orig is None:
-            for dd in range(d, D + 1):
-                idx = off[dd] + s + k ** d * np.arange(k ** (dd - d))
-                idx = idx[t["exists"][idx] != 0]
-                t["g"][idx] = self._default_g(dd)
-                t["beta"][idx] = self.hn_beta_vec
-            return
-        t["g"][i] = orig.h_g
-        t["beta"][i] = orig.h_beta_vec
-        if d == D:
-            t["leaf"][i] = 1
-            t["g"][i] = 0.0
-        elif orig.leaf:
-            t["leaf"][i] = 1
-        else:
-            t["leaf"][i] = 0
-            for c in range(k):
-                ci = off[d + 1] + s + c * k ** d
-                if not t["exists"][ci]:
-                    t["exists"][ci], t["g"][ci], t["beta"][ci], t["leaf"][ci] = 1, 0.5, 0.5, 0
-                self._scatter_tree(t, d + 1, s + c * k ** d, orig.children[c])
+        return _nodes.hn_root(self, _Node)
 
     # ---- hyperparameters ---------------------------------------------------------------------------------------------------
     def set_h0_params(self, h0_g=None, h0_beta_vec=None, h0_root=None):
@@ -357,18 +308,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if hn_root is not None:
             if type(hn_root) is not _Node:
                 raise ParameterFormatError("hn_root must be an instance of contexttree._Node")
-            if self._sparse:
-                _sparse.set_hn_root(self, hn_root)
-            else:
-                eng = self._eng()
-                if not self._has_root:
-                    eng.clear()
-                t = eng.get_tables()
-                if not self._has_root:
-                    t["exists"][0], t["g"][0], t["beta"][0], t["leaf"][0] = 1, 0.5, 0.5, 0
-                self._scatter_tree(t, 0, 0, hn_root)
-                eng.set_tables(t)
-                self._has_root = True
+            _nodes.set_hn_root(self, hn_root)
         self.calc_pred_dist(np.zeros(self.c_d_max, dtype=int))
         return self
 
@@ -376,70 +316,52 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         return {"hn_g": self.hn_g, "hn_beta_vec": self.hn_beta_vec, "hn_root": self.hn_root}
 
     # ---- learning ----------------------------------------------------------------------------------------------------------
-    def update_posterior(self, x):
-        """ref:712-731 in batch form; a refused sample changes nothing."""
+    def _adopt_sample(self, x):
+        """What ``update_posterior`` and ``pred_and_update_sequence`` accept as a sample, on the engine's device."""
         if _check._is_int(x) and x >= 0:
             x = np.asarray([x])
         if _check.sample_kind(x) != "i":
             raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
         if (x.numel() if hasattr(x, "numel") else x.size) == 0:
             np.max(np.zeros(0))          # the reference's x.max() of an empty sample: ValueError
+        return self._eng().adopt(x)
+
+    def _refuse_bad_symbols(self, xd, bad):
+        """``bad`` symbols were counted outside 0..c_k-1: the reference's message for a negative one, else for a large one."""
+        if bad > 0:
+            if self._eng().any_negative(xd):
+                raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
+            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+
+    def _ensure_root(self):
+        """A model without a tree gets its root, with the defaults, before a path or the MAP sweep starts from it."""
+        if not self._has_root:
+            eng = self._eng()
+            eng.clear()
+            eng.scatter([self._store.address(0, 0)], [self.hn_g], [self.hn_beta_vec], [1], [0])
+            self._has_root = True
+
+    def update_posterior(self, x):
+        """ref:712-731 in batch form; a refused sample changes nothing."""
+        xd = self._adopt_sample(x)
         eng = self._eng()
-        xd = eng.adopt(x)
         if not self._has_root:
             eng.clear()
         n, bad = eng.update(xd, self.hn_g, self.hn_beta_vec)
-        if bad > 0:
-            if eng.any_negative(xd):
-                raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
-            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+        self._refuse_bad_symbols(xd, bad)
         self._has_root = True
         return self
 
     def estimate_params(self, loss="0-1", visualize=True, filename=None, format=None):
-        """The MAP tree (ref:733-831) from ``ctree_map``'s table; only the pruned tree is built.  Plotting is out of scope:
-        pass ``visualize=False``.  Unlike the reference, the default-valued nodes that its sweep appends to ``hn_root`` are
-        not added to the posterior."""
+        """The MAP tree (ref:733-831) from the engine's ``map_leaf`` flags; only the pruned tree is built.  Plotting is out
+        of scope: pass ``visualize=False``.  Unlike the reference, the default-valued nodes that its sweep appends to
+        ``hn_root`` are not added to the posterior."""
         if loss != "0-1":
             raise CriteriaError("Unsupported loss function! This function supports only \"0-1\".")
         if visualize:
             raise NotImplementedError(_ctree.PLOT_MSG)
-        eng = self._eng()
-        if not self._has_root:
-            eng.clear()
-            eng.scatter([self._root_index()], [self.hn_g], [self.hn_beta_vec], [1], [0])
-            self._has_root = True
-        if self._sparse:
-            return _sparse.map_tree(self, _Node)
-        ml = eng.map_leaf(self.hn_g)
-        t = eng.get_tables()
-        k, D, off = self.c_k, self.c_d_max, self._off
-
-        def build(d, s, parent_g):
-            i = off[d] + s
-            node = _Node(d, k)
-            if t["exists"][i]:
-                node.h_g, beta = float(t["g"][i]), t["beta"][i]
-            else:
-                # (ref:755-762: a missing child that its parent's rule makes a leaf keeps hn_g even at the maximal depth)
-                by_rule = d == D and parent_g is not None and 1.0 - parent_g > parent_g * self.hn_g ** (
-                    (k ** (D - d + 1) - 1) / (k - 1) - 1)
-                node.h_g, beta = (self.hn_g if d < D or by_rule else 0.0), self.hn_beta_vec
-            node.h_beta_vec[:] = beta
-            if np.all(beta > 1):
-                node.theta_vec[:] = (beta - 1) / (np.sum(beta) - k)
-            else:
-                warnings.warn("MAP estimate of theta_vec doesn't exist for the current h_beta_vec.", ResultWarning)
-                node.theta_vec = None
-            if ml[i]:
-                node.leaf = True
-            else:
-                below = float(t["g"][i]) if t["exists"][i] else None
-                for c in range(k):
-                    node.children[c] = build(d + 1, s + c * k ** d, below)
-            return node
-
-        return build(0, 0, None)
+        self._ensure_root()
+        return _nodes.map_tree(self, _Node)
 
     def visualize_posterior(self, filename=None, format=None, h_params=False):
         raise NotImplementedError(_ctree.PLOT_MSG)
@@ -454,31 +376,13 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if x.max() >= self.c_k:
             raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
 
-    def _path(self, x):
-        """The D + 1 (or fewer) rows that the context before x[-1] selects, missing ones created with the defaults as
-        ref:956-965 does.  Returns (indices, g, beta, leaf)."""
-        if self._sparse:
-            return _sparse.path(self, x)
-        i = x.shape[0] - 1
-        depth = min(i, self.c_d_max)
-        idx, key = [0], 0
-        for d in range(depth):
-            key += int(x[i - d - 1]) * self.c_k ** d
-            idx.append(self._off[d + 1] + key)
-        g, beta, exists, leaf = self._eng().gather(idx)
-        g, beta, leaf = g.copy(), beta.copy(), leaf.copy()
-        for d in range(depth + 1):
-            if not exists[d]:
-                g[d], beta[d], leaf[d] = self._default_g(d), self.hn_beta_vec, d == self.c_d_max
-        return idx, g, beta, leaf
-
     def calc_pred_dist(self, x):
         """ref:954-989: the mixture over the path of the context x[:-1] (x[-1] is the position to predict)."""
         self._check_context(x)
         if not self._has_root:
             self.p_theta_vec[:] = self.hn_beta_vec / self.hn_beta_vec.sum()
             return self
-        idx, g, beta, leaf = self._path(x)
+        idx, g, beta, leaf = _nodes.path(self, x)
         p = beta[-1] / beta[-1].sum()
         for d in range(len(idx) - 2, -1, -1):
             p = (1 - g[d]) * beta[d] / beta[d].sum() + g[d] * p
@@ -496,12 +400,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def pred_and_update(self, x, loss="KL"):
         """ref:1016-1067: predict x[-1] from the context before it, then fold it in; one path, host work."""
         self._check_context(x)
-        eng = self._eng()
-        if not self._has_root:
-            eng.clear()
-            eng.scatter([self._root_index()], [self.hn_g], [self.hn_beta_vec], [1], [0])
-            self._has_root = True
-        idx, g, beta, leaf = self._path(x)
+        self._ensure_root()
+        idx, g, beta, leaf = _nodes.path(self, x)
         a = int(x[-1])
         p = beta[-1] / beta[-1].sum()
         beta[-1, a] += 1
@@ -512,7 +412,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
             g[d] = g[d] * p[a] / mixed[a]
             p = mixed
         self.p_theta_vec[:] = p
-        eng.scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
+        self._eng().scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
         return self.make_prediction(loss=loss)
 
     def pred_and_update_sequence(self, x, loss="KL", *, code_length=False, chunk_bytes=None):
@@ -537,20 +437,11 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
                 raise CriteriaError("loss=None returns the code lengths alone: pass code_length=True with it.")
         elif not (isinstance(loss, str) and loss in ("KL", "0-1")):
             raise CriteriaError("Unsupported loss function! This function supports \"0-1\" and \"KL\".")
-        if _check._is_int(x) and x >= 0:
-            x = np.asarray([x])
-        if _check.sample_kind(x) != "i":
-            raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
-        if (x.numel() if hasattr(x, "numel") else x.size) == 0:
-            np.max(np.zeros(0))          # the reference's x.max() of an empty sample: ValueError
-        as_numpy = isinstance(x, np.ndarray)
+        xd = self._adopt_sample(x)
+        as_numpy = not hasattr(x, "numel")          # (an int or a NumPy array: what is left once a tensor is ruled out)
         eng = self._eng()
-        xd = eng.adopt(x)
         n, bad = (int(v) for v in eng.count(xd)[:2].cpu())
-        if bad > 0:
-            if eng.any_negative(xd):
-                raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
-            raise DataFormatError(f"x.max() must smaller than c_k:{self.c_k}")
+        self._refuse_bad_symbols(xd, bad)
         if self._seq_pass is None:
             make = self._ctseq_pass_factory
             self._seq_pass = make(eng) if make is not None else _ctseq.SequencePass(eng)

@@ -1,38 +1,13 @@
 // include/ctree.h: argument checks, the layout of the level tables and of the scratch, and the launches of ctree_kernels.h.
 #include "../../include/ctree.h"
 #include "ctree_kernels.h"
-#include "entry.h"
-
-#include <cmath>
+#include "ctree_shape.h"
 
 namespace ctree {
 using namespace entry;
+using namespace ctree_shape;
 ENTRY_SAME_CODES(CTREE);
 static thread_local Err g_err = {""};
-
-// Sizes of a (k, D) tree; pw[d] = k^d, off[d] = first entry of level d in an all-levels table.
-struct Shape {
-    int64_t pw[26], off[27];
-    int64_t bins, nodes, upper;       // k^(D+1); entries of all levels; entries of levels 0..D-1
-};
-
-// 0 = fine, CTREE_EINVAL / CTREE_EUNSUPPORTED otherwise (no message set).
-static int shape_of(int k, int D, Shape* sh) {
-    if (k < 1 || D < 1) return CTREE_EINVAL;
-    if (k > CTREE_MAX_K || D > 24) return CTREE_EUNSUPPORTED;
-    int64_t p = 1;
-    sh->off[0] = 0;
-    for (int d = 0; d <= D; ++d) {
-        sh->pw[d] = p;
-        sh->off[d + 1] = sh->off[d] + p;
-        p *= k;
-        if (p > CTREE_MAX_SLOTS) return CTREE_EUNSUPPORTED;
-    }
-    sh->bins = p;
-    sh->nodes = sh->off[D + 1];
-    sh->upper = sh->off[D];
-    return CTREE_OK;
-}
 
 static int check_shape(const char* who, int k, int D, Shape* sh) {
     const int rc = shape_of(k, D, sh);
@@ -53,9 +28,8 @@ static int elem_size(int d) { return d == CTREE_U8 ? 1 : d == CTREE_I32 ? 4 : 8;
 template <typename T>
 static int launch_count(const void* x_dev, int64_t n, int k, int D, const Shape& sh, void* out_dev, void* work_dev,
                         hipStream_t st) {
-    int64_t span = (n + kMaxSlabs - 1) / kMaxSlabs;
-    if (span < kMinSpan) span = kMinSpan;
-    const int S = (int)((n + span - 1) / span);
+    int64_t span;
+    const int S = slab_span(n, kMaxSlabs, kMinSpan, &span);
     int64_t* out = (int64_t*)out_dev;
     if (lds_path(sh)) {
         hipLaunchKernelGGL((count_kernel<T, true>), dim3(S), dim3(kThreads), sizeof(unsigned long long) * (size_t)sh.bins, st,
@@ -72,13 +46,6 @@ static int launch_count(const void* x_dev, int64_t n, int k, int D, const Shape&
     if (int rc = g_err.launched("count_kernel launch")) return rc;
     hipLaunchKernelGGL(count_combine_kernel, dim3(1), dim3(kThreads), 0, st, (const int64_t*)work_dev, S, (int64_t)1, n, out);
     return g_err.launched("count_combine_kernel launch");
-}
-
-// hn_g^((k^(D-depth) - 1)/(k - 1) - 1), the reference's price of a full subtree under a missing child of a node at `depth`
-// (:757), in the host's binary64 pow as there; k = 1 takes the limit D - depth of the geometric sum.
-static double subtree_pow(double hn_g, int k, int D, int depth, const Shape& sh) {
-    const double m = k > 1 ? (double)(sh.pw[D - depth] - 1) / (double)(k - 1) : (double)(D - depth);
-    return std::pow(hn_g, m - 1.0);
 }
 }  // namespace ctree
 
@@ -161,8 +128,8 @@ int ctree_map(int k, int D, const void* g_dev, const void* exists_dev, double hn
     const uint8_t* ex = (const uint8_t*)exists_dev;
     uint8_t* ml = (uint8_t*)map_leaf_dev;
     for (int d = D; d >= 0; --d) {
-        const double pw_here = d < D ? subtree_pow(hn_g, k, D, d, sh) : 1.0;
-        const double pw_parent = d > 0 ? subtree_pow(hn_g, k, D, d - 1, sh) : 1.0;
+        const double pw_here = d < D ? subtree_pow(hn_g, k, D, d) : 1.0;
+        const double pw_parent = d > 0 ? subtree_pow(hn_g, k, D, d - 1) : 1.0;
         // (the neighbouring levels' pointers are not read at d = D and d = 0; they point at this level's tables there)
         const int dc = d < D ? d + 1 : d, dp = d > 0 ? d - 1 : d;
         hipLaunchKernelGGL(map_level_kernel, dim3(grid_of(sh.pw[d], kThreads)), dim3(kThreads), 0, st, k, d, D, sh.pw[d],

@@ -1,32 +1,14 @@
 // include/ctseq.h: argument checks, the layout of the scratch, and the launches of ctseq_kernels.h, one group per level.
 #include "../../include/ctseq.h"
-#include "../../include/ctree.h"
 #include "ctseq_kernels.h"
-#include "entry.h"
+#include "ctree_shape.h"
 
 namespace ctseq {
 using namespace entry;
+using ctree_shape::Shape;           // the pass works on ctree.h's tables: their layout and limit
+using ctree_shape::shape_of;
 ENTRY_SAME_CODES(CTSEQ);
 static thread_local Err g_err = {""};
-
-// pw[d] = k^d, off[d] = first entry of level d in an all-levels table (ctree.h's layout and limit).
-struct Shape {
-    int64_t pw[26], off[27];
-};
-
-static int shape_of(int k, int D, Shape* sh) {
-    if (k < 1 || D < 1) return CTSEQ_EINVAL;
-    if (k > CTREE_MAX_K || D > 24) return CTSEQ_EUNSUPPORTED;
-    int64_t p = 1;
-    sh->off[0] = 0;
-    for (int d = 0; d <= D; ++d) {
-        sh->pw[d] = p;
-        sh->off[d + 1] = sh->off[d] + p;
-        p *= k;
-        if (p > CTREE_MAX_SLOTS) return CTSEQ_EUNSUPPORTED;
-    }
-    return CTSEQ_OK;
-}
 
 // The scratch, in 8-byte slots from its start.  int32 arrays take half a slot per entry.
 struct Layout {

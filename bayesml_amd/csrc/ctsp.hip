@@ -1,12 +1,12 @@
 // include/ctsp.h: argument checks, key widths and capacity planning in plain C++, and the launches of ctsp_kernels.h.
 #include "../../include/ctsp.h"
 #include "ctsp_kernels.h"
-#include "entry.h"
-
-#include <cmath>
+#include "ctree_shape.h"
 
 namespace ctsp {
 using namespace entry;
+using ctree_shape::slab_span;
+using ctree_shape::subtree_pow;
 ENTRY_SAME_CODES(CTSP);
 static thread_local Err g_err = {""};
 
@@ -68,23 +68,11 @@ static int64_t level_size(int k, int level) {
 
 static int elem_size(int d) { return d == CTSP_U8 ? 1 : d == CTSP_I32 ? 4 : 8; }
 
-// hn_g^((k^(D-depth) - 1)/(k - 1) - 1) as in ctree.hip; k^(D-depth) in binary64 (exact where the dense engine runs)
-static double subtree_pow(double hn_g, int k, int D, int depth) {
-    double m = (double)(D - depth);
-    if (k > 1) {
-        double p = 1.0;
-        for (int j = 0; j < D - depth; ++j) p *= (double)k;
-        m = (p - 1.0) / (double)(k - 1);
-    }
-    return std::pow(hn_g, m - 1.0);
-}
-
 template <typename T>
 static int launch_count(const void* x_dev, int64_t n, int k, int b, int D, const int64_t* off, u64* key, u64* cnt,
                         int64_t* status, hipStream_t st) {
-    int64_t span = (n + kMaxSlabs - 1) / kMaxSlabs;
-    if (span < kMinSpan) span = kMinSpan;
-    const int S = (int)((n + span - 1) / span);
+    int64_t span;
+    const int S = slab_span(n, kMaxSlabs, kMinSpan, &span);
     hipLaunchKernelGGL((count_kernel<T>), dim3(S), dim3(kThreads), 0, st, (const T*)x_dev, n, span, k, b, D, key + off[D],
                        off[D + 1] - off[D], cnt + off[D] * k, status);
     return g_err.launched("ctsp count_kernel launch");

@@ -65,6 +65,10 @@ def batch_update(x, k, D, nodes, hn_g, hn_beta_vec):
         else:
             shift = b * (D - d - 1)
             S = np.array([sum(logw.get(int(s) | (c << shift), 0.0) for c in range(k)) for s in uniq])
+            if d == 0:
+                # (bit for bit the dense oracle's sum: NumPy adds the rows of its [k, k^d] table one after another, as
+                # above, but sums the single column of the root, [k, 1], in blocks once k >= 8)
+                S = np.array([[logw.get(c << shift, 0.0)] for c in range(k)]).sum(0)
             bp, lead = b0.copy(), np.zeros(len(uniq))
             hk = inv[0]                  # sample i = d is the head sample of this level
             lead[hk] = np.log(b0[hk, x[d]] / b0[hk].sum())
@@ -83,6 +87,25 @@ def batch_update(x, k, D, nodes, hn_g, hn_beta_vec):
             leaf = nodes[(d, s)][2] if ex[j] else int(d == D)
             nodes[(d, s)] = [float(newg[j]), b0[j] + cnt[j], leaf]
     return nodes
+
+
+def map_nodes(k, D, nodes, hn_g):
+    """map_leaf of every node of the dict (the root must exist): ``contexttree_oracle.map_tables`` on existing nodes, the
+    same products in the same order.  Returns {(level, key): bool}."""
+    from contexttree_oracle import subtree_pow
+    b, val, ml = bits(k), {}, {}
+    for d, s in sorted(nodes, reverse=True):            # children before parents
+        if d == D:
+            val[(d, s)], ml[(d, s)] = 1.0, True
+            continue
+        g = nodes[(d, s)][0]
+        stop, thr = 1.0 - g, g * subtree_pow(hn_g, k, D, d)
+        prod = 1.0
+        for c in range(k):
+            prod = prod * val.get((d + 1, s | (c << (b * (D - d - 1)))), stop if stop > thr else thr)
+        ml[(d, s)] = bool(stop > g * prod)
+        val[(d, s)] = stop if ml[(d, s)] else g * prod
+    return ml
 
 
 # ---- canonical lists ---------------------------------------------------------------------------------------------------------
@@ -247,6 +270,75 @@ def drive(mod, case, inp, make=None):
     out["trace_p"] = np.stack([m.pred_and_update(tr[:j + 1], loss="KL").copy() for j in range(len(tr))])
     out["final_nodes"] = np.asarray(len(tree_to_nodes(m.hn_root, k, D)))
     return out, m
+
+
+def planted_tree(mod, k, D):
+    """A tree for ``set_hn_params(hn_root=...)`` that takes every branch of the superposition: the all-zero context as a
+    chain down to a node at depth D (given h_g = 0.9 there, which the superposition must turn into 0), every other child
+    of the chain absent, except that the last child of the root is a leaf above the maximal depth (where a posterior that
+    has seen data holds an inner node: a flipped leaf)."""
+    node_cls = mod._contexttree._Node
+    chain = [node_cls(d, k, 0.15 + 0.05 * d) for d in range(D + 1)]
+    for d, node in enumerate(chain):
+        node.h_beta_vec[:] = np.arange(1, k + 1) + d / 4.0
+        if d < D:
+            node.children[0] = chain[d + 1]
+    chain[D].h_g = 0.9
+    if k > 1 and D > 1:
+        flipped = node_cls(1, k, 0.35)
+        flipped.h_beta_vec[:] = 3.0
+        flipped.leaf = True
+        chain[0].children[k - 1] = flipped
+    return chain[0]
+
+
+def extended_drive(mod, case, inp, make=None):
+    """``drive``, then on its model: superpose ``planted_tree``, pickle and unpickle, one more ``pred_and_update`` and the
+    MAP tree.  Returns ``drive``'s dict with these stages added."""
+    import pickle
+    import warnings
+    k, D = case["k"], case["D"]
+    out, m = drive(mod, case, inp, make=make)
+
+    def snap(stage, model):
+        for name, a in tree_to_lists(model.hn_root, k, D).items():
+            out[f"{stage}_{name}"] = a
+    m.set_hn_params(hn_root=planted_tree(mod, k, D))
+    snap("planted", m)
+    out["planted_p"] = m.p_theta_vec.copy()
+    m = pickle.loads(pickle.dumps(m))
+    snap("unpickled", m)
+    out["unpickled_p"] = m.pred_and_update(inp["trace_x"][:D + 1], loss="KL").copy()
+    snap("unpickled_after", m)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for name, a in map_tree_to_lists(m.estimate_params(loss="0-1", visualize=False), k, D).items():
+            out[f"planted_map_{name}"] = a
+    return out, m
+
+
+# ---- c_k = 1 with an absent child: tests/golden/make_golden_contexttree_k1.py (the reference) and the tests ------------------
+K1_CASES = [dict(name="k1_d2", D=2, h0_g=0.7, n=0), dict(name="k1_d3", D=3, h0_g=0.7, n=0),
+            dict(name="k1_d2_stops_above", D=2, h0_g=0.3, n=0), dict(name="k1_d2_one_symbol", D=2, h0_g=0.9, n=1)]
+
+
+def k1_drive(mod, case, make=None):
+    """A fresh c_k = 1 model.  With n = 0 it is given a root that is not a leaf and whose only child is absent: the
+    superposition creates the child (and the closing calc_pred_dist the all-zero path above the maximal depth), so the node
+    at depth D - 1 exists and its child at depth D is missing.  With n = 1 it learns one symbol instead: the root alone
+    exists.  Returns JSON-ready lists: the posterior, and the MAP tree or the outcome of ``estimate_params``."""
+    from contexttree_oracle import outcome
+    D = case["D"]
+    m = (make or mod.LearnModel)(1, D, case["h0_g"], np.array([1.5]))
+    if case["n"]:
+        m.update_posterior(np.zeros(case["n"], dtype=int))
+    else:
+        root = mod._contexttree._Node(0, 1, 0.9)
+        root.h_beta_vec[:] = 2.5
+        m.set_hn_params(hn_root=root)
+    posterior, got = {n: a.tolist() for n, a in tree_to_lists(m.hn_root, 1, D).items()}, {}
+    what = outcome(lambda: got.update(map_tree_to_lists(m.estimate_params(loss="0-1", visualize=False), 1, D)))
+    return dict(posterior=posterior, map_outcome=what, map={n: a.tolist() for n, a in got.items()})
 
 
 def stage_lists(fx, stage):
