@@ -561,17 +561,44 @@ static __global__ void reduce_stats_kernel(const double* __restrict__ slabs, int
 }
 
 // The same for the list M-step's chunk slabs (mstep.h): component k owns slabs plan[k] .. plan[k + 1] - 1.
+// runs = G > 0: the slabs of the persistent form instead - the runs that met component k, from the first batch's to the last
+// batch's, run g's slab at g + k; the batch prefix comes from counts[] as in the list kernel (K <= 256), plan is not read.
 // accumulate: stats += the sum (the settled-row cache taking in a pass's delta lists); add: stats = the sum + add (the
 // statistics of a pass = its lists + the cache), add in the layout of stats.
 static __global__ void reduce_chunks_kernel(const double* __restrict__ slabs, const int* __restrict__ plan, int K, int D, int T,
-                                     double* __restrict__ stats, int accumulate = 0, const double* __restrict__ add = nullptr) {
+                                     double* __restrict__ stats, int accumulate = 0, const double* __restrict__ add = nullptr,
+                                     const int* __restrict__ counts = nullptr, int runs = 0) {
     const int k = blockIdx.y;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int P = tri_pairs(T);
     const int L = slab_len(T);
+    __shared__ int s_range[2];
+    if (runs > 0) {                                   // (uniform over the grid: every thread reaches the barrier)
+        if (threadIdx.x < 64) {
+            // batches before component k, in it, and in all: lane l adds components l, l + 64, ... (integers: any order)
+            long long before = 0, mine = 0, all = 0;
+            for (int q = threadIdx.x; q < K; q += 64) {
+                const int b = (counts[q] + kMlistBatch - 1) / kMlistBatch;
+                all += b;
+                if (q < k) before += b;
+                if (q == k) mine = b;
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                before += __shfl_xor(before, o);
+                mine += __shfl_xor(mine, o);
+                all += __shfl_xor(all, o);
+            }
+            if (threadIdx.x == 0) {
+                const long long G = mlist_runs_for(runs, all);
+                s_range[0] = mine > 0 ? mlist_run_of(before, all, G) + k : 0;
+                s_range[1] = mine > 0 ? mlist_run_of(before + mine - 1, all, G) + k + 1 : 0;
+            }
+        }
+        __syncthreads();
+    }
     if (e >= P * 256 + 16 * T + 2) return;
     double v = 0.0;
-    const int c0 = plan[k], c1 = plan[k + 1];
+    const int c0 = runs > 0 ? s_range[0] : plan[k], c1 = runs > 0 ? s_range[1] : plan[k + 1];
     // (a component has ~70 slabs at the benchmark shape and the loop was a chain of dependent round trips to HBM: eight
     // loads in flight, added in the same chunk order - the same bits)
     int c = c0;

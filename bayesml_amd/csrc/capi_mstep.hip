@@ -40,6 +40,7 @@ struct Mstep {
     bool vec;
     MstepPlan plan{};
     const char* name = "";
+    int runs = 0;          // list form: the runs of its last launch (launch_mstep_list), 0 = chunks
 
     MstepFacts facts() const;
     void begin_phase() const {
@@ -116,7 +117,7 @@ int Mstep::reduce_and_note() {
                            ws->gen_second, (int)plan.S, ws->K, ws->D, ws->T, stats_dev);
     } else if (plan.reduce == kReduceChunks) {
         hipLaunchKernelGGL(reduce_chunks_kernel, dim3((plan.elems + 255) / 256, ws->K), dim3(256), 0, st, ws->slabs, ws->plan_m,
-                           ws->K, ws->D, ws->T, stats_dev, 0, plan.add_cache ? ws->cache : nullptr);
+                           ws->K, ws->D, ws->T, stats_dev, 0, plan.add_cache ? ws->cache : nullptr, ws->counts, runs);
     } else {
         hipLaunchKernelGGL(reduce_stats_kernel, dim3((plan.elems + 255) / 256, ws->K), dim3(256), 0, st, ws->slabs, (int)plan.S,
                            ws->K, ws->D, ws->T, stats_dev);
@@ -145,12 +146,12 @@ int Mstep::apply_delta(const MstepListArgs& la, int nblk) {
     ld.direct_r = 3;
     const char* dname = "";
     span_begin(ws, kSpanMstepMain, st);
-    const hipError_t e = launch_mstep_list(ws->T, (int)plan.dgrid, st, ld, &dname);
+    const hipError_t e = launch_mstep_list(ws->T, (int)plan.dgrid, st, ld, &dname, &runs);
     span_end(ws, st);
     if (e != hipSuccess) return fail(GMMVB_EHIP, "settled-row delta launch", e);
     span_begin(ws, kSpanReduce, st);
     hipLaunchKernelGGL(reduce_chunks_kernel, dim3((plan.elems + 255) / 256, ws->K), dim3(256), 0, st, ws->slabs, ws->plan_m, ws->K,
-                       ws->D, ws->T, ws->cache, 1, nullptr);
+                       ws->D, ws->T, ws->cache, 1, nullptr, ws->counts, runs);
     span_end(ws, st);
     return GMMVB_OK;
 }
@@ -175,6 +176,7 @@ int Mstep::run_lists() {
     begin_phase();
     MstepListArgs la{ws->xc, ws->lnrho, ws->lse, ws->lists, ws->npad, ws->counts, ws->plan_m, plan.cap_chunks, plan.r_min,
                      ws->npad, ws->K, ws->slabs};
+    la.num_cu = ws->num_cu, la.runs_cap = ws->opt_mlist_runs;
     if (plan.rows != kRowsCentred) {
         la.x32 = (const float*)(plan.rows == kRowsXp32 ? ws->xp : x_dev);
         la.ldx = plan.list_ldx;
@@ -201,7 +203,7 @@ int Mstep::run_lists() {
     ws->active_lists = plan.active_lists;
     if (plan.clear_blk_fresh) ws->blk_fresh = false;
     span_begin(ws, kSpanMstepMain, st);
-    const hipError_t e = launch_mstep_list(ws->T, (int)plan.grid, st, la, &name);
+    const hipError_t e = launch_mstep_list(ws->T, (int)plan.grid, st, la, &name, &runs);
     span_end(ws, st);
     ++ws->passes[plan.counter];
     if (e != hipSuccess) return fail(GMMVB_EHIP, "mstep launch", e);

@@ -125,5 +125,16 @@ __device__ __forceinline__ double sum_wave(double v) {
 // Slab written by one M-step wave for one (row split, component):
 //   [ P tile pairs x (4 regs x 64 lanes) | a[16 T] | ns | h | pad ]
 __host__ __device__ constexpr int slab_len(int t) { return tri_pairs(t) * 256 + 16 * t + 16; }
+// runs of the list M-step (mstep.h): batches of kMlistBatch list entries, run g of G takes batches [g B / G, (g + 1) B / G);
+// the run that holds batch b is the largest g with g B / G <= b (G = mlist_runs_for(..) <= B: no run is empty)
+constexpr int kMlistBatch = 64;
+// ... and no more runs than leave each kMlistRunMin batches: a run's slab is slab_len doubles written and read back, as much
+// as the rows of 2.3 batches at T = 8 - below a few batches per run a launch is its slabs (the delta lists of a settled pass)
+constexpr int kMlistRunMin = 4;
+__host__ __device__ inline long long mlist_runs_for(long long G, long long B) {
+    const long long most = (B + kMlistRunMin - 1) / kMlistRunMin;
+    return G < most ? G : most;
+}
+__host__ __device__ inline int mlist_run_of(long long b, long long B, long long G) { return (int)(((b + 1) * G + B - 1) / B - 1); }
 
 }  // namespace gmmvb

@@ -430,8 +430,8 @@ constexpr int kGatherTiles = 8;
 
 // The work distribution is read from the device (no host knowledge of the list lengths):
 // plan[k] = index of component k's first chunk of kGatherTiles x 8 waves x 16 NB list entries, plan[K] = total
-// (gather_plan_kernel, records.h).  A fixed grid of persistent workgroups takes contiguous runs of chunks, restaging
-// the component image only when the component changes.
+// (gather_plan_kernel, records.h).  A fixed grid of persistent workgroups takes contiguous ranges of the chunks' tiles,
+// restaging the component image only when the component changes.
 // EXIT: candidates of a selection round - rows carry a relevance threshold thr[row], see estep_component_exit.
 template <int T, typename XT, bool VEC, bool EXIT>
 __global__ __launch_bounds__(512) void estep_gather_dev_f64(const XT* __restrict__ x, int64_t ldx, int D,
@@ -454,14 +454,21 @@ __global__ __launch_bounds__(512) void estep_gather_dev_f64(const XT* __restrict
     const int n = lane & 15, g = lane >> 4;
     for (int k = threadIdx.x; k <= K; k += 512) s_first[k] = plan[k];
     __syncthreads();
-    const int total = s_first[K];
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int c0 = (int)blockIdx.x * per;
-    const int c1 = c0 + per < total ? c0 + per : total;
+    // The unit handed out is the workgroup tile (8 waves x 16 NB entries), numbered chunk by chunk: workgroup b takes
+    // tiles [b TT / G, (b + 1) TT / G) of the TT = total x kGatherTiles, so its range may start and end inside a chunk
+    // and no workgroup has more than one tile above the mean (whole chunks left up to kGatherTiles of them idle).
+    const int64_t tiles = (int64_t)s_first[K] * kGatherTiles;
+    const int64_t t_lo = (int64_t)blockIdx.x * tiles / (int64_t)gridDim.x;
+    const int64_t t_hi = ((int64_t)blockIdx.x + 1) * tiles / (int64_t)gridDim.x;
+    const int c0 = (int)(t_lo / kGatherTiles);
+    const int c1 = (int)((t_hi + kGatherTiles - 1) / kGatherTiles);
     int k = 0, kcur = -1;
     unsigned long long my_exits = 0;                     // pairs of this wave that took the early way out (statistics)
-    for (int c = c0; c < c1; ++c) {
+    for (int c = t_lo < t_hi ? c0 : c1; c < c1; ++c) {
         while (s_first[k + 1] <= c) ++k;                 // component of chunk c (empty components are skipped)
+        // this workgroup's tiles of chunk c: [tile_a, tile_b), the whole chunk except at the two ends of its range
+        const int tile_a = t_lo > (int64_t)c * kGatherTiles ? (int)(t_lo - (int64_t)c * kGatherTiles) : 0;
+        const int tile_b = t_hi < ((int64_t)c + 1) * kGatherTiles ? (int)(t_hi - (int64_t)c * kGatherTiles) : kGatherTiles;
         if (k != kcur) {
             __syncthreads();                             // every wave is done with the previous image
             const double* src = img + (int64_t)k * IMG + lane * 2;
@@ -480,18 +487,25 @@ __global__ __launch_bounds__(512) void estep_gather_dev_f64(const XT* __restrict
         // Software pipeline over the chunk's tiles (round 4): while tile t is computed, the rows of tile t + 1 are in flight
         // (second register set) and the list entries of tile t + 2 have been requested - before, a wave's list -> rows -> MFMA
         // chain was serial and only the other waves of the SIMD covered it.  Every iteration issues the same loads (tiles
-        // past the list's end repeat its last entry and skip the arithmetic), so the compiler's in-order vmcnt stays exact.
+        // past the list's end or outside this workgroup's tiles [tile_a, tile_b) repeat the last entry that is its own and skip
+        // the arithmetic), so the compiler's in-order vmcnt stays exact.
+        // (offsets inside the chunk, 32 bits: o_hi >= 1 - a component with a chunk has an entry in it)
+        const int o_lo = tile_a * (NW * 16 * NB);
+        const int64_t left_k = count - chunk0;
+        const int o_hi = left_k < tile_b * (NW * 16 * NB) ? (int)left_k : tile_b * (NW * 16 * NB);
+        const int* chunk_list = list + chunk0;
         auto rows_of = [&](int t, int64_t (&ld)[NB], int64_t (&stv)[NB]) {
-            const int64_t e0 = chunk0 + ((int64_t)t * NW + wave) * 16 * NB;
+            const int o0 = (t * NW + wave) * 16 * NB;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                const int64_t e = e0 + 16 * nb + n;
-                const int row = list[e < count ? e : count - 1];
+                const int o = o0 + 16 * nb + n;
+                const bool mine = o >= o_lo && o < o_hi;
+                const int row = chunk_list[mine ? o : o_hi - 1];
                 ld[nb] = row;
-                stv[nb] = e < count ? row : -1;
+                stv[nb] = mine ? row : -1;
             }
         };
-        auto live = [&](int t) { return chunk0 + ((int64_t)t * NW + wave) * 16 * NB < count; };
+        auto live = [&](int t) { return t >= tile_a && t < tile_b && (t * NW + wave) * 16 * NB < o_hi; };
         auto thr_of = [&](const int64_t (&ld)[NB], float (&tv)[NB]) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) tv[nb] = EXIT ? thr[ld[nb]] : 0.0f;

@@ -128,7 +128,11 @@ struct MstepListArgs {
     int64_t npad; int K; double* slabs;
     const float* x32 = nullptr; int64_t ldx = 0; int64_t n_rows = 0; int D = 0; const double* pivot = nullptr;   // f32 rows instead of xc
     int direct_r = 0;      // 3: delta lists of the settled-row cache (weights +-1 from the entries' sign bits)
+    int num_cu = 0;        // compute units of the device, and GMMVB_MLIST_RUNS (0: no cap): how many runs the lists are cut into
+    int runs_cap = 0;
 };
-hipError_t launch_mstep_list(int T, int grid, hipStream_t st, const MstepListArgs& a, const char** name);
+// *runs = G > 0: the persistent form ran - G runs over the lists' batches, the slab of (run g, component k) at g + k
+// (reduce_chunks_kernel with runs = G); 0: the chunk form over `plan` (the slab capacity leaves fewer than two runs)
+hipError_t launch_mstep_list(int T, int grid, hipStream_t st, const MstepListArgs& a, const char** name, int* runs);
 
 }  // namespace gmmvb

@@ -20,6 +20,7 @@
 // registers for the whole row range (f64 accumulation, no flush needed) and are written once as a
 // slab in register order; reduce_stats sums slabs over row splits in a fixed order.
 #pragma once
+#include <type_traits>
 #include <utility>
 #include "common.h"
 
@@ -789,21 +790,110 @@ static __global__ void mstep_plan_kernel(const int* __restrict__ counts, int K, 
     for (int k = threadIdx.x; k <= K; k += blockDim.x) plan[k] = sc[k];
 }
 
-template <int T>
-__global__ __launch_bounds__(64 * mstep_waves(T, true)) void mstep_list_f64(
+// ---- runs: the persistent form of the list kernels ---------------------------------------------------------------------
+// A chunk is at least r_min entries of one component: a launch with little work keeps a few wave groups busy for a whole
+// chunk each, the last round of chunks runs with most of the chip idle, and every chunk's slab is written and read back.
+// The persistent form cuts the same lists into G runs instead, G = the wave groups the device holds at once (fewer for
+// a small grid, or under GMMVB_MLIST_RUNS).  Batch space: the components' lists laid end to end, each padded to whole
+// batches of 64 entries (the granule mstep_body loads indices in), B batches in all; run g takes batches
+// [g B / G', (g + 1) B / G') with G' = min(G, ceil(B / kMlistRunMin)) - every run has work, no two differ by more than one batch.  A run walks
+// its batches in order, one mstep_body call per component it meets (the accumulators stay in registers along a
+// component), and writes slab g + k for component k: the batches are ordered by component, so g + k strictly increases
+// along the (run, component) segments - unique, and at most G + K - 2 (the launch keeps G + K - 1 <= the slab capacity).
+// The partition is a pure function of counts[], G and the batch size: no workgroup waits for another, nothing is atomic,
+// and reduce_chunks_kernel (aux_kernels.h) derives from the same numbers which runs met component k and adds their slabs in
+// ascending run order - run-to-run identical.
+// (kMlistBatch and mlist_run_of: common.h, shared with the reduction)
+
+// s_bf[k] = first batch of component k, s_bf[K] = B (K <= 256; every thread of the workgroup calls it, at least one wave)
+__device__ __forceinline__ void mlist_batch_prefix(const int* __restrict__ counts, int K, int* s_bf /*[257]*/) {
+    if (threadIdx.x < 64) {
+        const int l = threadIdx.x;
+        int b[4], sum = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = 4 * l + u;
+            b[u] = k < K ? (counts[k] + kMlistBatch - 1) / kMlistBatch : 0;
+            sum += b[u];
+        }
+        int inc = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o);
+            if (l >= o) inc += v;
+        }
+        int at = inc - sum;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = 4 * l + u;
+            if (k <= K) s_bf[k] = at;
+            at += b[u];
+        }
+        if (4 * l + 4 == K) s_bf[K] = at;
+    }
+    __syncthreads();
+}
+
+// Run g of G over the batch prefix in LDS: body(k, lo, hi, out) for every component the run meets (wave uniform).
+template <int T, typename Body>
+__device__ __forceinline__ void mlist_walk_run(const int* s_bf, const int* __restrict__ counts, int K, int g, int G,
+                                               double* __restrict__ slabs, Body&& body) {
+    const int B = __builtin_amdgcn_readfirstlane(s_bf[K]);
+    G = (int)mlist_runs_for(G, B);
+    if (g >= G) return;                               // (B = 0: no run at all)
+    // (the 64-bit divisions run on the vector ALU: their wave-uniform results go back to scalar registers, or the loop's
+    // state would sit in vector registers through every row loop)
+    int b = __builtin_amdgcn_readfirstlane((int)((long long)g * B / G));
+    const int b1 = __builtin_amdgcn_readfirstlane((int)((long long)(g + 1) * B / G));
+    int k = 0;
+    while (b < b1) {
+        while (__builtin_amdgcn_readfirstlane(s_bf[k + 1]) <= b) ++k;      // (empty components are skipped)
+        const int first = __builtin_amdgcn_readfirstlane(s_bf[k]), next = __builtin_amdgcn_readfirstlane(s_bf[k + 1]);
+        const int be = next < b1 ? next : b1;
+        const int64_t lo = (int64_t)(b - first) * kMlistBatch;
+        int64_t hi = (int64_t)(be - first) * kMlistBatch;
+        if (hi > counts[k]) hi = counts[k];
+        body(k, lo, hi, slabs + (int64_t)(g + k) * slab_len(T));
+        b = be;
+    }
+}
+
+// T = 8 sits at the 256 registers of two waves per SIMD (144 of them accumulators); the run loop around mstep_body must not
+// cost the second wave, so the register allocator is held to it (no scratch: the build's resource report is checked).
+#define MLIST_TWO_WAVES(T, RUNS) __attribute__((amdgpu_waves_per_eu((RUNS) && (T) == 8 ? 2 : 1)))
+
+template <int T, bool RUNS>
+__global__ __launch_bounds__(64 * mstep_waves(T, true)) MLIST_TWO_WAVES(T, RUNS) void mstep_list_f64(
     const double* __restrict__ xc,         // [npad + 64][16 T] centred rows
     const double* __restrict__ lnrho,      // [K][npad]
     const double* __restrict__ lse,        // [npad]
     const int* __restrict__ lists,         // [K][cap] active rows, ascending
     int64_t cap,
     const int* __restrict__ counts,        // [K] list lengths
-    const int* __restrict__ plan,          // [K + 2] chunk plan
+    const int* __restrict__ plan,          // [K + 2] chunk plan (RUNS: not read)
     int64_t npad, int K,
-    double* __restrict__ slabs /*[chunks][slab_len(T)]*/, int direct_r /*0, or 3: delta lists*/) {
+    double* __restrict__ slabs /*[chunks][slab_len(T)]*/, int direct_r /*0, or 3: delta lists*/, int runs /*RUNS: G*/) {
     constexpr int WS = mstep_ws(T);
     constexpr int KPW = mstep_waves(T, true) / WS;
+    __shared__ int s_bf[RUNS ? 257 : 1];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = (int)blockIdx.x * KPW + wave / WS;
+    const int sub = wave % WS;
+    // one (component, list range) -> one slab, by wave SUB of the component's WS
+    auto body = [&](auto sub_c, int k, int64_t lo, int64_t hi, double* out) {
+        mstep_body<T, WS, decltype(sub_c)::value, double, true, true, true>(xc, 16 * T, npad, 16 * T, nullptr, lnrho + (int64_t)k * npad, lse,
+                                                                            nullptr, lo, hi, direct_r, out, lists + (int64_t)k * cap);
+    };
+    auto body0 = [&](int k, int64_t lo, int64_t hi, double* out) { body(std::integral_constant<int, 0>{}, k, lo, hi, out); };
+    auto body1 = [&](int k, int64_t lo, int64_t hi, double* out) { body(std::integral_constant<int, WS - 1>{}, k, lo, hi, out); };
+    if constexpr (RUNS) {
+        mlist_batch_prefix(counts, K, s_bf);
+        if (WS == 1 || sub == 0)                     // (a loop of its own per wave of the pair: one body inside each)
+            mlist_walk_run<T>(s_bf, counts, K, c, runs, slabs, body0);
+        else
+            mlist_walk_run<T>(s_bf, counts, K, c, runs, slabs, body1);
+        return;
+    }
     if (c >= plan[K]) return;
     int k = 0;
     {
@@ -816,37 +906,45 @@ __global__ __launch_bounds__(64 * mstep_waves(T, true)) void mstep_list_f64(
         k = lo;
     }
     const int R = plan[K + 1];
-    const int sub = wave % WS;
     const int64_t lo = (int64_t)(c - plan[k]) * R;
     int64_t hi = lo + R;
     if (hi > counts[k]) hi = counts[k];
-    const double* lr = lnrho + (int64_t)k * npad;
-    const int* list = lists + (int64_t)k * cap;
-    double* out = slabs + (int64_t)c * slab_len(T);
-    if constexpr (WS == 1) {
-        mstep_body<T, 1, 0, double, true, true, true>(xc, 16 * T, npad, 16 * T, nullptr, lr, lse, nullptr, lo, hi, direct_r, out, list);
-    } else {
-        if (sub == 0)
-            mstep_body<T, 2, 0, double, true, true, true>(xc, 16 * T, npad, 16 * T, nullptr, lr, lse, nullptr, lo, hi, direct_r, out, list);
-        else
-            mstep_body<T, 2, 1, double, true, true, true>(xc, 16 * T, npad, 16 * T, nullptr, lr, lse, nullptr, lo, hi, direct_r, out, list);
-    }
+    if (WS == 1 || sub == 0)
+        body0(k, lo, hi, slabs + (int64_t)c * slab_len(T));
+    else
+        body1(k, lo, hi, slabs + (int64_t)c * slab_len(T));
 }
 
 // The same over the caller's f32 rows (or the workspace's regrouped f32 copy) instead of the centred f64 copy: with
 // one or two active components per row every listed row is read about once, so the kernel's HBM traffic is the rows
 // themselves - 4 D bytes instead of 8 D - and the conversion and pivot subtraction (the very operations that made the
 // centred copy: identical values) ride in the shadow of the MFMAs.
-template <int T>
-__global__ __launch_bounds__(64 * mstep_waves(T, true)) void mstep_list_x32_f64(
+template <int T, bool RUNS>
+__global__ __launch_bounds__(64 * mstep_waves(T, true)) MLIST_TWO_WAVES(T, RUNS) void mstep_list_x32_f64(
     const float* __restrict__ x, int64_t ldx, int64_t n_rows, int D, const double* __restrict__ pivot,
     const double* __restrict__ lnrho, const double* __restrict__ lse, const int* __restrict__ lists, int64_t cap,
     const int* __restrict__ counts, const int* __restrict__ plan, int64_t npad, int K, double* __restrict__ slabs,
-    int direct_r /*0, or 3: delta lists*/) {
+    int direct_r /*0, or 3: delta lists*/, int runs /*RUNS: G*/) {
     constexpr int WS = mstep_ws(T);
     constexpr int KPW = mstep_waves(T, true) / WS;
+    __shared__ int s_bf[RUNS ? 257 : 1];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = (int)blockIdx.x * KPW + wave / WS;
+    const int sub = wave % WS;
+    auto body = [&](auto sub_c, int k, int64_t lo, int64_t hi, double* out) {
+        mstep_body<T, WS, decltype(sub_c)::value, float, true, false, true, true>(x, ldx, n_rows, D, pivot, lnrho + (int64_t)k * npad, lse,
+                                                                                  nullptr, lo, hi, direct_r, out, lists + (int64_t)k * cap);
+    };
+    auto body0 = [&](int k, int64_t lo, int64_t hi, double* out) { body(std::integral_constant<int, 0>{}, k, lo, hi, out); };
+    auto body1 = [&](int k, int64_t lo, int64_t hi, double* out) { body(std::integral_constant<int, WS - 1>{}, k, lo, hi, out); };
+    if constexpr (RUNS) {
+        mlist_batch_prefix(counts, K, s_bf);
+        if (WS == 1 || sub == 0)
+            mlist_walk_run<T>(s_bf, counts, K, c, runs, slabs, body0);
+        else
+            mlist_walk_run<T>(s_bf, counts, K, c, runs, slabs, body1);
+        return;
+    }
     if (c >= plan[K]) return;
     int k = 0;
     {
@@ -859,21 +957,13 @@ __global__ __launch_bounds__(64 * mstep_waves(T, true)) void mstep_list_x32_f64(
         k = lo;
     }
     const int R = plan[K + 1];
-    const int sub = wave % WS;
     const int64_t lo = (int64_t)(c - plan[k]) * R;
     int64_t hi = lo + R;
     if (hi > counts[k]) hi = counts[k];
-    const double* lr = lnrho + (int64_t)k * npad;
-    const int* list = lists + (int64_t)k * cap;
-    double* out = slabs + (int64_t)c * slab_len(T);
-    if constexpr (WS == 1) {
-        mstep_body<T, 1, 0, float, true, false, true, true>(x, ldx, n_rows, D, pivot, lr, lse, nullptr, lo, hi, direct_r, out, list);
-    } else {
-        if (sub == 0)
-            mstep_body<T, 2, 0, float, true, false, true, true>(x, ldx, n_rows, D, pivot, lr, lse, nullptr, lo, hi, direct_r, out, list);
-        else
-            mstep_body<T, 2, 1, float, true, false, true, true>(x, ldx, n_rows, D, pivot, lr, lse, nullptr, lo, hi, direct_r, out, list);
-    }
+    if (WS == 1 || sub == 0)
+        body0(k, lo, hi, slabs + (int64_t)c * slab_len(T));
+    else
+        body1(k, lo, hi, slabs + (int64_t)c * slab_len(T));
 }
 
 }  // namespace gmmvb

@@ -5,6 +5,7 @@
 #include "mstep.h"
 #include "launch.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace gmmvb {
@@ -76,24 +77,58 @@ hipError_t launch_mstep(int T, int x_is_f64, bool vec, bool pre, int grid, hipSt
     return hipErrorInvalidValue;
 }
 
+// Wave groups the device holds at once, for the persistent form of the list kernels (asked of the runtime once per kernel).
+template <int T, bool X32>
+static int list_groups_resident(int num_cu) {
+    static int per_cu = 0;
+    if (per_cu == 0) {
+        int n = 0;
+        const void* fn = X32 ? reinterpret_cast<const void*>(&mstep_list_x32_f64<T, true>)
+                             : reinterpret_cast<const void*>(&mstep_list_f64<T, true>);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64 * mstep_waves(T, true), 0) != hipSuccess || n < 1) n = 1;
+        per_cu = n;
+    }
+    return per_cu * num_cu * (mstep_waves(T, true) / mstep_ws(T));
+}
+
 template <int T>
-static hipError_t go_list(int grid, hipStream_t st, const MstepListArgs& a) {
+static hipError_t go_list(int grid, hipStream_t st, const MstepListArgs& a, int* runs) {
+    constexpr int KPW = mstep_waves(T, true) / mstep_ws(T);
+    const dim3 threads(64 * mstep_waves(T, true));
+    // G: what is resident at once, never more than the planned grid, GMMVB_MLIST_RUNS, and G + K - 1 slabs must fit
+    int64_t G = a.x32 ? list_groups_resident<T, true>(a.num_cu) : list_groups_resident<T, false>(a.num_cu);
+    G = std::min<int64_t>(G, (int64_t)grid * KPW);
+    const int64_t room = (int64_t)a.cap_chunks - a.K + 1;
+    if (a.runs_cap > 0) G = std::min<int64_t>(G, a.runs_cap);
+    G = std::min(G, room);
+    if (room >= 2 && G >= 1 && a.K <= 256) {
+        *runs = (int)G;
+        const int g = (int)((G + KPW - 1) / KPW);
+        if (a.x32)
+            hipLaunchKernelGGL((mstep_list_x32_f64<T, true>), dim3(g), threads, 0, st, a.x32, a.ldx, a.n_rows, a.D, a.pivot, a.lnrho,
+                               a.lse, a.lists, a.cap, a.counts, a.plan, a.npad, a.K, a.slabs, a.direct_r, (int)G);
+        else
+            hipLaunchKernelGGL((mstep_list_f64<T, true>), dim3(g), threads, 0, st, a.xc, a.lnrho, a.lse, a.lists, a.cap, a.counts,
+                               a.plan, a.npad, a.K, a.slabs, a.direct_r, (int)G);
+        return hipGetLastError();
+    }
+    *runs = 0;
     hipLaunchKernelGGL(mstep_plan_kernel, dim3(1), dim3(64), 0, st, a.counts, a.K, a.cap_chunks, a.r_min, a.plan);
     if (a.x32)
-        hipLaunchKernelGGL((mstep_list_x32_f64<T>), dim3(grid), dim3(64 * mstep_waves(T, true)), 0, st, a.x32, a.ldx, a.n_rows,
-                           a.D, a.pivot, a.lnrho, a.lse, a.lists, a.cap, a.counts, a.plan, a.npad, a.K, a.slabs, a.direct_r);
+        hipLaunchKernelGGL((mstep_list_x32_f64<T, false>), dim3(grid), threads, 0, st, a.x32, a.ldx, a.n_rows, a.D, a.pivot, a.lnrho,
+                           a.lse, a.lists, a.cap, a.counts, a.plan, a.npad, a.K, a.slabs, a.direct_r, 0);
     else
-        hipLaunchKernelGGL((mstep_list_f64<T>), dim3(grid), dim3(64 * mstep_waves(T, true)), 0, st, a.xc, a.lnrho, a.lse,
-                           a.lists, a.cap, a.counts, a.plan, a.npad, a.K, a.slabs, a.direct_r);
+        hipLaunchKernelGGL((mstep_list_f64<T, false>), dim3(grid), threads, 0, st, a.xc, a.lnrho, a.lse, a.lists, a.cap, a.counts,
+                           a.plan, a.npad, a.K, a.slabs, a.direct_r, 0);
     return hipGetLastError();
 }
 
 #define LCASE(TT)                                        \
     case TT:                                             \
         *name = a.x32 ? "mstep_list_f64<T=" #TT ",x=f32>" : "mstep_list_f64<T=" #TT ",centred-f64>"; \
-        return go_list<TT>(grid, st, a);
+        return go_list<TT>(grid, st, a, runs);
 
-hipError_t launch_mstep_list(int T, int grid, hipStream_t st, const MstepListArgs& a, const char** name) {
+hipError_t launch_mstep_list(int T, int grid, hipStream_t st, const MstepListArgs& a, const char** name, int* runs) {
     switch (T) {
         LCASE(1) LCASE(2) LCASE(3) LCASE(4) LCASE(5) LCASE(6) LCASE(7) LCASE(8)
     }

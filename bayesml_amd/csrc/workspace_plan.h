@@ -54,6 +54,7 @@ struct WorkspaceOptions {
     bool opt_calibrate = true;         // GMMVB_POLICY_CALIBRATE=0: the scaled literals only
     bool opt_quiet_tiles = true;       // GMMVB_QUIET_TILES=0: no tile-level shortcuts for tiles of settled rows (workspace.h)
     bool opt_mlist_xc = false;         // GMMVB_MLIST_XC=1: the list M-step reads the centred f64 copy, never f32 rows (mstep_plan.h)
+    int opt_mlist_runs = 0;            // GMMVB_MLIST_RUNS=<n>: at most n runs in the list M-step (mstep.h); 0: what the device holds
     bool opt_debug = false;            // GMMVB_DEBUG=2
 
     // lookup: const char* (const char* name), null for an unset name - std::getenv in the library
@@ -81,6 +82,7 @@ struct WorkspaceOptions {
         o.opt_calibrate = not_zero(dev("GMMVB_POLICY_CALIBRATE"));
         o.opt_quiet_tiles = not_zero(dev("GMMVB_QUIET_TILES"));
         if (const char* v = dev("GMMVB_MLIST_XC")) o.opt_mlist_xc = v[0] == '1';
+        if (const char* v = dev("GMMVB_MLIST_RUNS")) o.opt_mlist_runs = std::max(0, std::atoi(v));
         o.opt_debug = lookup("GMMVB_DEBUG") && lookup("GMMVB_DEBUG")[0] == '2';
         return o;
     }
