@@ -390,11 +390,15 @@ int Pass::sweep_bounds(bool proof, bool own_round) {
         note_hip(ws, hipMemsetAsync(ws->exit_ctr + 1, 0, sizeof(unsigned long long), st));
         // (the tile state is void after any pass that rewrote the bounds wholesale: the first sweep after it
         // opens every column and takes stock)
-        dispatch_mask_words(ws->K, [&](auto wc) {        // (mask words as a compile-time constant)
-            hipLaunchKernelGGL((rec_sweep_kernel<true, true, decltype(wc)::value>), dim3(sel_grid), dim3(kSelRows), 0, st, ws->ub32,
-                               ws->lnrho, ws->npad, n_rows, ws->K, ws->drift, ws->cvec, ws->khat, rec, ws->masks, ws->blk,
-                               ws->epart, ws->opart, lock, ws->dlock, ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all, own_fresh,
-                               ws->tmeta, tmeta_was_valid ? 0 : 1, ws->exit_ctr + 1, ws->ppart, tile_loose, quiet_ctr);
+        const int run = sweep_run_length(ws->K, ws->opt_sweep_run);
+        dispatch_mask_words(ws->K, [&](auto wc) {        // (mask words and run length as compile-time constants)
+            dispatch_sweep_run(run, [&](auto rr) {
+                constexpr int WC = decltype(wc)::value, R = WC <= 2 ? decltype(rr)::value : 1;
+                hipLaunchKernelGGL((rec_sweep_kernel<true, true, WC, R>), dim3((sel_grid + R - 1) / R), dim3(kSelRows), 0, st,
+                                   ws->ub32, ws->lnrho, ws->npad, n_rows, ws->K, ws->drift, ws->cvec, ws->khat, rec, ws->masks,
+                                   ws->blk, ws->epart, ws->opart, lock, ws->dlock, ws->rthr, ws->lcomp, pmask, ws->rblk, proof_all,
+                                   own_fresh, ws->tmeta, tmeta_was_valid ? 0 : 1, ws->exit_ctr + 1, ws->ppart, tile_loose, quiet_ctr);
+            });
         });
         tmeta_kept = true;
         quiet_swept = tile_loose != nullptr;

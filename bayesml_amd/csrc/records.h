@@ -334,7 +334,16 @@ __device__ __forceinline__ float wave_max_f32(float v) {
 // (Three and four mask words: five waves per SIMD asked for - 96 registers and 24 bytes of scratch outside the column loop
 // instead of 108: the kernel lives on the other waves hiding its per-pair LDS and memory waits; six - 80 registers, 144
 // bytes of scratch - loses again.  3.79 -> 3.35 ms at K = 256.)
-template <bool PREV, bool LAZY = false, int WC = 0>
+// R > 1 (LAZY): a workgroup goes through a run of R consecutive tiles, one after the other (the grid is ceil(tiles / R);
+// the last run may be short), and adds the columns it opened to col_ctr ONCE, at the end of the run.  With a tile per
+// workgroup that counter was the kernel's floor: 39 063 additions to one address per pass at the benchmark shape, which
+// the memory side appears to take one at a time (13.6 ns each) - 0.53 ms whatever the rows did, against 0.36 ms without them
+// (profiles/sweep_chain.md).  The per-component constants and the zeroed counters are set up once per run as well.
+// Whatever a tile writes it writes as the one-tile form does, at the tile's own index; no workgroup waits on another and
+// none lives longer than its R tiles.  The tiles of a run are written out (do_tile below is instantiated R times), not
+// looped over: around a loop the compiler holds everything that does not depend on the tile in registers - twice the
+// registers of a tile.  R = 1 is the one-tile order of work.
+template <bool PREV, bool LAZY = false, int WC = 0, int R = 1>
 __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep_kernel(float* __restrict__ ub, const double* __restrict__ u, int64_t npad,
                                                              int64_t n_rows, int K,
                                                              const double* __restrict__ drift,
@@ -362,6 +371,7 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
                                                              unsigned long long* __restrict__ quiet_ctr = nullptr /*+= tiles without
                                                                  one (GMMVB_DEBUG=2)*/) {
     static_assert(!LAZY || PREV, "the lazy sweep is a form of the PREV sweep");
+    static_assert(R == 1 || LAZY, "runs of tiles: the lazy form only");
     __shared__ int wcnt[4][256];
     __shared__ int pcnt[4][256];
     __shared__ float4 sp[256];          // gamma (1 - 1e-6) down, delta up, c' up, c old down  (LAZY: composed since the column was written)
@@ -380,7 +390,22 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
     __shared__ float s_skip[LAZY ? 4 : 1];                 // per wave (of columns): largest bound among the closed columns
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int W = WC > 0 ? WC : (K + 63) / 64;
-    const int64_t n = (int64_t)blockIdx.x * kSelRows + tid;
+    const unsigned tiles = (unsigned)((n_rows + kSelRows - 1) / kSelRows), tile0 = blockIdx.x * R;
+    // one tile, the r-th of the run; returns the columns this wave's lane 0 reports opened.
+    // Shared memory over the tiles of a run (a tile has four barriers at the lazy form: A behind the row's reference value,
+    // B behind s_thr, C behind the columns' state, D in front of the tile's read-out; A and D at the others):
+    //   per run    sfirst, sq, sc, s_delta (and sp at the forms that are not lazy): written by tile 0 in front of its A, read only;
+    //   per tile, written and read between the tile's own barriers: s_thr (A | B), sp / s_open / s_redo / s_keep / s_skip
+    //              (B | C, read up to the tile's end), s_any / s_red / wsum (C | D, read behind D) - the next tile's first write
+    //              to any of them lies behind its own A, B or C, so behind every read of this tile;
+    //   per tile, handed over zeroed: wcnt / pcnt (written C | D, read behind D) and s_force (written A | B, read B | C) are
+    //              zeroed again behind D by the one thread that reads entry k last, and the next tile's first write to them
+    //              lies behind its A.
+    auto do_tile = [&](auto rc) __attribute__((always_inline)) {
+    constexpr unsigned r = decltype(rc)::value;
+    const unsigned tile = tile0 + r;
+    const int64_t n = (int64_t)tile * kSelRows + tid;
+    unsigned opened = 0u;
     const bool valid = n < n_rows;
     // what the row needs from global memory and does not depend on the component constants is requested before the first
     // barrier: the kernel is a chain of dependent loads per workgroup (0.67 ms of its 1.0 ms at the benchmark shape do not
@@ -401,18 +426,26 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
         }
     }
     if constexpr (LAZY)
-        if (tid < K && !tmeta_reset) meta_pre = tmeta[(int64_t)blockIdx.x * K + tid];
-    for (int k = lane; k < K; k += 64) wcnt[wave][k] = pcnt[wave][k] = 0;
+        if (tid < K && !tmeta_reset) meta_pre = tmeta[(int64_t)tile * K + tid];
     float4 step = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int k = tid; k < K; k += kSelRows) {
-        sfirst[k] = (own_fresh && own_first(drift[3 * K + k], drift[K + k])) ? 1 : 0;
-        const double g = drift[k] * (1.0 - 1e-6);
-        step = make_float4(g > 0.0 ? f32_down(g) : 0.0f, f32_up(drift[K + k]), f32_up(c_new[k]), f32_down(drift[2 * K + k]));
-        if constexpr (!LAZY) sp[k] = step;
-        s_delta[k] = step.y;
-        sq[k] = make_float2(f32_up(drift[3 * K + k] * (1.0 + 1e-6)), f32_down(c_new[k]));
-        sc[k] = c_new[k];
-        if constexpr (LAZY) s_force[k] = 0;
+    if constexpr (r == 0) {
+        for (int k = lane; k < K; k += 64) wcnt[wave][k] = pcnt[wave][k] = 0;
+        for (int k = tid; k < K; k += kSelRows) {
+            sfirst[k] = (own_fresh && own_first(drift[3 * K + k], drift[K + k])) ? 1 : 0;
+            const double g = drift[k] * (1.0 - 1e-6);
+            step = make_float4(g > 0.0 ? f32_down(g) : 0.0f, f32_up(drift[K + k]), f32_up(c_new[k]), f32_down(drift[2 * K + k]));
+            if constexpr (!LAZY) sp[k] = step;
+            s_delta[k] = step.y;
+            sq[k] = make_float2(f32_up(drift[3 * K + k] * (1.0 + 1e-6)), f32_down(c_new[k]));
+            sc[k] = c_new[k];
+            if constexpr (LAZY) s_force[k] = 0;
+        }
+    } else {
+        // the counters were left zeroed and the constants in place by the tile before: only this lane's step is made again
+        for (int k = tid; k < K; k += kSelRows) {
+            const double g = drift[k] * (1.0 - 1e-6);
+            step = make_float4(g > 0.0 ? f32_down(g) : 0.0f, f32_up(drift[K + k]), f32_up(c_new[k]), f32_down(drift[2 * K + k]));
+        }
     }
     // ---- the row's reference value ------------------------------------------------------------------------------------
     const double ninf = -__builtin_huge_val();
@@ -513,7 +546,7 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
             col_keep = col_open && !unknown && !col_forced;
             sp[k] = comp;
             if (!col_open) {
-                tmeta[(int64_t)blockIdx.x * K + k] = make_float4(meta.x, comp.x, comp.y, meta.w);
+                tmeta[(int64_t)tile * K + k] = make_float4(meta.x, comp.x, comp.y, meta.w);
                 skip = col_bound;
             }
         }
@@ -526,7 +559,7 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
             s_redo[wave] = rb;
             s_keep[wave] = kb2;
             s_skip[wave] = skip;
-            if (col_ctr && ob) atomicAdd(col_ctr, (unsigned long long)__builtin_popcountll(ob));
+            if (col_ctr) opened = (unsigned)__builtin_popcountll(ob);
         }
         __syncthreads();
     }
@@ -799,29 +832,53 @@ __global__ __launch_bounds__(kSelRows, (LAZY && WC >= 3 ? 5 : 1)) void rec_sweep
             const int k = tid, w = k >> 6;
             const bool any = (((s_any[0][w] | s_any[1][w] | s_any[2][w] | s_any[3][w]) >> (k & 63)) & 1ull) != 0ull;
             if (col_keep && !any) {                        // nothing was written: the column stays in its frame
-                tmeta[(int64_t)blockIdx.x * K + k] = make_float4(meta.x, comp.x, comp.y, meta.w);
+                tmeta[(int64_t)tile * K + k] = make_float4(meta.x, comp.x, comp.y, meta.w);
             } else {
                 float tub = col_bound;                     // nothing replaced: the carry of the largest entry is the largest
                 if (col_redo) tub = fmaxf(fmaxf(s_red[0][k], s_red[1][k]), fmaxf(s_red[2][k], s_red[3][k]));
                 if (col_forced || any) tub = __builtin_huge_valf();
-                tmeta[(int64_t)blockIdx.x * K + k] = make_float4(tub, 1.0f, 0.0f, sq[k].y);
+                tmeta[(int64_t)tile * K + k] = make_float4(tub, 1.0f, 0.0f, sq[k].y);
             }
         }
     }
     for (int k = tid; k < K; k += kSelRows) {
-        blk_cnt[blk_at(k, blockIdx.x, K)] = wcnt[0][k] + wcnt[1][k] + wcnt[2][k] + wcnt[3][k];
-        if (pmask) pblk[blk_at(k, blockIdx.x, K)] = pcnt[0][k] + pcnt[1][k] + pcnt[2][k] + pcnt[3][k];
+        blk_cnt[blk_at(k, tile, K)] = wcnt[0][k] + wcnt[1][k] + wcnt[2][k] + wcnt[3][k];
+        if (pmask) pblk[blk_at(k, tile, K)] = pcnt[0][k] + pcnt[1][k] + pcnt[2][k] + pcnt[3][k];
+        if constexpr (R > 1) {
+            // the counters and the forced columns start the next tile as they started this one (its first writes to them
+            // lie behind its first barrier)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) wcnt[v][k] = pcnt[v][k] = 0;
+            if constexpr (LAZY) s_force[k] = 0;
+        }
     }
     if (tid == 0) {
-        epart[blockIdx.x] = (double)(wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3]);
-        opart[blockIdx.x] = (double)(wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3]);
-        if (ppre) ppre[blockIdx.x] = (double)(wsum[2][0] + wsum[2][1] + wsum[2][2] + wsum[2][3]);
+        epart[tile] = (double)(wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3]);
+        opart[tile] = (double)(wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3]);
+        if (ppre) ppre[tile] = (double)(wsum[2][0] + wsum[2][1] + wsum[2][2] + wsum[2][3]);
         if (tile_loose) {
             const int loose = wsum[3][0] + wsum[3][1] + wsum[3][2] + wsum[3][3];
-            tile_loose[blockIdx.x] = loose;
+            tile_loose[tile] = loose;
             if (quiet_ctr && loose == 0) atomicAdd(quiet_ctr, 1ull);
         }
     }
+    return opened;
+    };
+    unsigned opened = do_tile(std::integral_constant<unsigned, 0>{});
+    if constexpr (R > 1) {
+        if (tile0 + 1 < tiles) {
+            opened += do_tile(std::integral_constant<unsigned, 1>{});
+            if constexpr (R > 2) {
+                static_assert(R == 4, "run lengths: 1, 2, 4");
+                if (tile0 + 2 < tiles) {
+                    opened += do_tile(std::integral_constant<unsigned, 2>{});
+                    if (tile0 + 3 < tiles) opened += do_tile(std::integral_constant<unsigned, 3>{});
+                }
+            }
+        }
+    }
+    if constexpr (LAZY)
+        if (lane == 0 && opened) atomicAdd(col_ctr, (unsigned long long)opened);
 }
 
 // After the proof round (estep_i8_proof over the pairs of pmask): every row the sweep flagged 8 has a lower bound of its

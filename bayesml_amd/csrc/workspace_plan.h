@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gmmvb.h"
@@ -55,6 +56,8 @@ struct WorkspaceOptions {
     bool opt_quiet_tiles = true;       // GMMVB_QUIET_TILES=0: no tile-level shortcuts for tiles of settled rows (workspace.h)
     bool opt_mlist_xc = false;         // GMMVB_MLIST_XC=1: the list M-step reads the centred f64 copy, never f32 rows (mstep_plan.h)
     int opt_mlist_runs = 0;            // GMMVB_MLIST_RUNS=<n>: at most n runs in the list M-step (mstep.h); 0: what the device holds
+    int opt_sweep_run = 0;             // GMMVB_SWEEP_RUN=<n>: the carried sweep's workgroups take runs of n tiles (records.h; the
+                                       // compiled length nearest below n, 1 = a tile per workgroup); 0: what the shape's default is
     bool opt_debug = false;            // GMMVB_DEBUG=2
 
     // lookup: const char* (const char* name), null for an unset name - std::getenv in the library
@@ -83,10 +86,28 @@ struct WorkspaceOptions {
         o.opt_quiet_tiles = not_zero(dev("GMMVB_QUIET_TILES"));
         if (const char* v = dev("GMMVB_MLIST_XC")) o.opt_mlist_xc = v[0] == '1';
         if (const char* v = dev("GMMVB_MLIST_RUNS")) o.opt_mlist_runs = std::max(0, std::atoi(v));
+        if (const char* v = dev("GMMVB_SWEEP_RUN")) o.opt_sweep_run = std::max(0, std::atoi(v));
         o.opt_debug = lookup("GMMVB_DEBUG") && lookup("GMMVB_DEBUG")[0] == '2';
         return o;
     }
 };
+
+// The carried sweep's run length (records.h: tiles per workgroup, and per addition to the opened-columns counter) as a
+// compile-time constant: 1, 2 or 4, at one and two mask words.  At three and four (K > 128) the one-tile form already
+// holds 96 registers and the written-out run goes to scratch: a tile per workgroup there, always.  GMMVB_SWEEP_RUN=n
+// (developer switch) picks the compiled length nearest below n.
+constexpr int kSweepRunDefault = 2;      // (measured, profiles/sweep_chain.md: 4 costs a resident workgroup and gains nothing more)
+inline int sweep_run_length(int K, int asked) {
+    if (K > 128) return 1;
+    const int want = asked > 0 ? asked : kSweepRunDefault;
+    return want >= 4 ? 4 : (want >= 2 ? 2 : 1);
+}
+template <typename F>
+inline void dispatch_sweep_run(int run, F&& f) {
+    if (run == 4) return f(std::integral_constant<int, 4>{});
+    if (run == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
+}
 
 // ---- shape ---------------------------------------------------------------------------------------------------------------
 // Sizes that live in the kernels' translation units, as numbers: the constants, then the values at this (K, D) and its tile
