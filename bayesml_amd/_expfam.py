@@ -148,7 +148,13 @@ class ExpfamPass:
 
 class PassOwner:
     """What the five LearnModels share: the keyword-only ``device``, the lazily made ``ExpfamPass`` (dropped on pickling),
-    and the private test seam ``_expfam_pass_factory`` (tests/fake_expfam_engine.py)."""
+    and the private test seam ``_expfam_pass_factory`` (tests/fake_expfam_engine.py).  The sequence pass behind
+    ``pred_and_update_sequence`` (``_expseq.SequencePass``) is made on first use, with its own seam
+    ``_expseq_pass_factory`` (tests/expfam_seq_oracle.py); both names are class attributes until then, so a model that
+    never calls the method keeps the instance ``__dict__`` and the pickles it always had."""
+
+    _seq_engine = None
+    _expseq_pass_factory = None
 
     def _init_pass(self, device):
         self._device = device
@@ -158,7 +164,16 @@ class PassOwner:
     def __getstate__(self):
         state = dict(self.__dict__)
         state["_engine"] = None
+        state.pop("_seq_engine", None)
         return state
+
+    def _seq_pass(self):
+        if self._expseq_pass_factory is not None:
+            return self._expseq_pass_factory()
+        if self._seq_engine is None:
+            from ._expseq import SequencePass
+            self._seq_engine = SequencePass(self._device)
+        return self._seq_engine
 
     def _pass(self):
         if self._expfam_pass_factory is not None:

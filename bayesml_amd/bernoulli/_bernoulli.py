@@ -10,7 +10,7 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _expfam as xf, base
+from .. import _check, _expfam as xf, _expseq as xs, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _LOSS_MSG = 'Unsupported loss function! This function supports "squared", "0-1", "abs", and "KL".'
@@ -194,6 +194,27 @@ class LearnModel(xf.PassOwner, base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x)
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", *, code_length=False):
+        """``[pred_and_update(x[i], loss) for i in range(n)]`` in one device pass (include/expseq.h): the exclusive prefix
+        counts of ones and zeros give ``p_theta`` of every position.  x is accepted and refused as ``update_posterior``
+        does it.  Returns float64 ``p_theta`` ("squared"), int64 ``p_theta > 0.5`` ("0-1", "abs") or float64 [n, 2]
+        ("KL"); with ``code_length`` also ``nats[i] = -ln p(x[i] | x[:i])``; ``loss=None`` returns the nats alone and
+        leaves ``p_theta``.  NumPy in, NumPy out; a tensor in, tensors on the device out."""
+        def fold(st):
+            self.hn_alpha += st[0]
+            self.hn_beta += st[1]
+
+        def predict(loss, params):
+            p_theta, = params
+            if loss == "squared":
+                return p_theta
+            if loss == "KL":
+                return xs.xp_of(p_theta).stack((1.0 - p_theta, p_theta), 1)
+            return xs.as_int64(p_theta > 0.5)
+
+        return xs.sequence(self, xs.BERNOULLI, x, loss, code_length, ("squared", "0-1", "abs", "KL"), _LOSS_MSG,
+                           lambda: self._counts(x, True), fold, (self.hn_alpha, self.hn_beta), predict)
 
     def calc_log_marginal_likelihood(self):
         from scipy.special import gammaln

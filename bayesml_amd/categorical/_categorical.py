@@ -13,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _expfam as xf, base
+from .. import _check, _expfam as xf, _expseq as xs, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _LOSS_MSG = 'Unsupported loss function! This function supports "squared", "0-1", and "KL".'
@@ -216,6 +216,53 @@ class LearnModel(xf.PassOwner, base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss, onehot)
         self.update_posterior(x, onehot)
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", onehot=True, *, code_length=False, chunk_bytes=None):
+        """``[pred_and_update(x[i], loss, onehot) for i in range(n)]`` in one device pass (include/expseq.h), x[i] being
+        the rows of a one-hot matrix or, with ``onehot=False``, indices.  x is accepted and refused as
+        ``update_posterior(x, onehot)`` does it.  Returns float64 rows [n, c_degree] ("squared", "KL"), or for "0-1" the
+        int64 one-hot rows of the first maximum (``onehot=False``: the int64 argmax [n]); with ``code_length`` also
+        ``nats[i] = -ln p(x[i] | x[:i])``; ``loss=None`` returns the nats alone, forms no [n, c_degree] array anywhere and
+        leaves ``p_theta_vec``.  The normaliser of position i is ``hn_alpha_vec.sum() + i``: it grows by exactly one per
+        position.  The sample is taken in chunks whose scratch stays within ``chunk_bytes`` (default 256 MiB); the counts
+        carried between chunks are integers, so the cut changes no bit."""
+        import torch
+        xs.check_sequence_loss(loss, code_length, ("squared", "0-1", "KL"), _LOSS_MSG)
+        counts = self._onehot_counts(x) if onehot else self._index_counts(x, True)
+        as_numpy = not isinstance(x, torch.Tensor)
+        c = self.c_degree
+        if not xf.is_array(x):
+            x = np.asarray([x], dtype=np.int64)
+        n = xf.size_of(x) // c if onehot else xf.size_of(x)
+        want = {"squared": "rows", "KL": "rows", "0-1": "argmax", None: None}[loss]
+        if n == 0:
+            zeros = (lambda shape, dt: np.zeros(shape, dtype=getattr(np, dt))) if as_numpy else (
+                lambda shape, dt: torch.zeros(shape, dtype=getattr(torch, dt), device=xs.out_device(self, x)))
+            pred = zeros((0, c), "float64") if want == "rows" else zeros((0,), "int64") if want == "argmax" else None
+            nats = zeros((0,), "float64")
+        else:
+            eng = self._seq_pass()
+            alpha0 = self.hn_alpha_vec.copy()
+            xd = eng.adopt(x, "i", c) if onehot else eng.adopt(x, "i")
+            pred, nats, _, _ = eng.run_categorical(xd, onehot, alpha0, want, bool(code_length), chunk_bytes)
+            if want is not None:
+                # the parameters of the last prediction, by the pass's own expression
+                last = int(xd[-1].argmax()) if onehot else int(xd[-1])
+                before = np.asarray(counts, dtype=np.int64).copy()
+                before[last] -= 1
+                self.p_theta_vec[:] = (alpha0 + before) / (alpha0.sum() + float(n - 1))
+            self.hn_alpha_vec[:] += counts
+            if as_numpy:
+                pred, nats = (None if t is None else xs.host(t) for t in (pred, nats))
+        if loss is None:
+            return nats
+        if loss == "0-1" and onehot:
+            if isinstance(pred, torch.Tensor):
+                pred = torch.zeros((n, c), dtype=torch.int64, device=pred.device).scatter_(1, pred[:, None], 1)
+            else:
+                am, pred = pred, np.zeros((n, c), dtype=np.int64)
+                pred[np.arange(n), am] = 1
+        return (pred, nats) if code_length else pred
 
     def calc_log_marginal_likelihood(self):
         from scipy.special import gammaln

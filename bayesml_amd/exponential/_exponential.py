@@ -11,7 +11,7 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _expfam as xf, base
+from .. import _check, _expfam as xf, _expseq as xs, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _LOSS_MSG = 'Unsupported loss function! This function supports "squared", "0-1", "abs", and "KL".'
@@ -196,6 +196,36 @@ class LearnModel(xf.PassOwner, base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x)
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", *, code_length=False):
+        """``[pred_and_update(x[i], loss) for i in range(n)]`` in one device pass (include/expseq.h): the exclusive prefix
+        sums give ``p_kappa`` and ``p_lambda`` of every position.  x is accepted and refused as ``update_posterior`` does
+        it.  Returns float64 means ("squared": NaN where ``p_kappa <= 1``, where the loop returns None, with one
+        ``ResultWarning`` for the call), zeros ("0-1"), medians ("abs"), or on the host the frozen Lomax over the
+        parameter arrays ("KL"); with ``code_length`` also ``nats[i] = -ln p(x[i] | x[:i])``; ``loss=None`` returns the
+        nats alone and leaves ``p_kappa`` and ``p_lambda``."""
+        def fold(st):
+            self.hn_alpha += st[0]
+            self.hn_beta += st[1]
+
+        def predict(loss, params):
+            p_kappa, p_lambda = params
+            xp = xs.xp_of(p_kappa)
+            if loss == "squared":
+                none = ~(p_kappa > 1)
+                if bool(none.any()):
+                    warnings.warn("Mean doesn't exist for the current p_kappa.", ResultWarning)
+                mean = p_lambda / xp.where(none, xp.ones_like(p_kappa), p_kappa - 1)
+                return xp.where(none, xp.full_like(p_kappa, np.nan), mean)
+            if loss == "0-1":
+                return xp.zeros_like(p_kappa)
+            if loss == "abs":
+                return p_lambda * (2.0 ** (1.0 / p_kappa) - 1)
+            from scipy.stats import lomax as ss_lomax
+            return ss_lomax(c=xs.host(p_kappa), scale=xs.host(p_lambda))
+
+        return xs.sequence(self, xs.EXPONENTIAL, x, loss, code_length, ("squared", "0-1", "abs", "KL"), _LOSS_MSG,
+                           lambda: self._sums(x, True), fold, (self.hn_alpha, self.hn_beta), predict)
 
     def calc_log_marginal_likelihood(self):
         from scipy.special import gammaln

@@ -11,7 +11,7 @@ import warnings
 
 import numpy as np
 
-from .. import _check, _expfam as xf, base
+from .. import _check, _expfam as xf, _expseq as xs, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _LOSS_MSG = 'Unsupported loss function! This function supports "squared", "0-1", "abs", and "KL".'
@@ -217,6 +217,24 @@ class LearnModel(xf.PassOwner, base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x)
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", *, code_length=False):
+        """``[pred_and_update(x[i], loss) for i in range(n)]`` in one device pass (include/expseq.h): the exclusive prefix
+        (count, mean, m2) about the pivot x[0] gives ``p_mu``, ``p_nu`` and ``p_lambda`` of every position.  x is accepted
+        and refused as ``update_posterior`` does it.  Returns float64 ``p_mu`` ("squared", "0-1", "abs") or on the host
+        the frozen Student-t over the parameter arrays ("KL"); with ``code_length`` also
+        ``nats[i] = -ln p(x[i] | x[:i])``; ``loss=None`` returns the nats alone and leaves ``p_mu``, ``p_nu`` and
+        ``p_lambda``."""
+        def predict(loss, params):
+            p_mu, p_nu, p_lambda = params
+            if loss != "KL":
+                return p_mu
+            from scipy.stats import t as ss_t
+            return ss_t(loc=xs.host(p_mu), scale=1.0 / np.sqrt(xs.host(p_lambda)), df=xs.host(p_nu))
+
+        return xs.sequence(self, xs.NORMAL, x, loss, code_length, ("squared", "0-1", "abs", "KL"), _LOSS_MSG,
+                           lambda: self._moments(x, True), lambda st: self._fold(*st),
+                           (self.hn_m, self.hn_kappa, self.hn_alpha, self.hn_beta), predict)
 
     def calc_log_marginal_likelihood(self):
         from scipy.special import gammaln

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .. import _check, _expfam as xf, base
+from .. import _check, _expfam as xf, _expseq as xs, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError
 
 _LOSS_MSG = 'Unsupported loss function! This function supports "squared", "0-1", "abs", and "KL".'
@@ -193,6 +193,27 @@ class LearnModel(xf.PassOwner, base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x)
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", *, code_length=False):
+        """``[pred_and_update(x[i], loss) for i in range(n)]`` in one device pass (include/expseq.h): the exclusive prefix
+        sums give ``p_r`` and ``p_theta`` of every position.  x is accepted and refused as ``update_posterior`` does it.
+        Returns the float64 means ("squared") or modes ("0-1"), on the host the medians ("abs") or the frozen
+        negative-binomial over the parameter arrays ("KL"); with ``code_length`` also ``nats[i] = -ln p(x[i] | x[:i])``;
+        ``loss=None`` returns the nats alone and leaves ``p_r`` and ``p_theta``."""
+        def predict(loss, params):
+            p_r, p_theta = params
+            if loss == "squared":
+                return p_r * p_theta / (1.0 - p_theta)
+            if loss == "0-1":
+                xp = xs.xp_of(p_r)
+                return xp.where(p_r > 1.0, xp.floor((p_r - 1.0) * p_theta / (1.0 - p_theta)), xp.zeros_like(p_r))
+            from scipy.stats import nbinom as ss_nbinom
+            p_r, p_theta = xs.host(p_r), xs.host(p_theta)
+            dist = ss_nbinom(n=p_r, p=(1.0 - p_theta))
+            return dist if loss == "KL" else ss_nbinom.median(n=p_r, p=(1.0 - p_theta))
+
+        return xs.sequence(self, xs.POISSON, x, loss, code_length, ("squared", "0-1", "abs", "KL"), _LOSS_MSG,
+                           lambda: self._sums(x, True), lambda st: self._fold(*st), (self.hn_alpha, self.hn_beta), predict)
 
     def calc_log_marginal_likelihood(self):
         from scipy.special import gammaln
