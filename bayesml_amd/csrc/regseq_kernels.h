@@ -115,8 +115,9 @@ static __global__ void block_scan_kernel(const double* __restrict__ slabs, int64
 }
 
 // ---- (3) -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void block_start_kernel(const double* __restrict__ start /*[D D + D + 3]*/, int D,
-                                                           double* states) {
+// (static: mvnseq.hip includes this header too)
+static __global__ __launch_bounds__(1024) void block_start_kernel(const double* __restrict__ start /*[D D + D + 3]*/, int D,
+                                                                  double* states) {
     __shared__ double dinv[16 * gmmvb::kDinvSize];
     __shared__ double sr[256], su[256];
     __shared__ double s_uu;

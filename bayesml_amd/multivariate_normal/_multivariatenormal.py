@@ -5,8 +5,9 @@ The conjugate update (ref:501-524) needs n, the sample mean and the scatter matr
 That pass is the GMM M-step kernel with a single component whose responsibilities are all one
 (``gmmvb_load_responsibilities`` + ``gmmvb_mstep``): ns = n, a = sum (x - p), B = sum (x - p)(x - p)^T about a
 pivot p, from which  x_bar = p + a/n  and  sum (x - x_bar)(x - x_bar)^T = B - a a^T / n.  Everything K-sized stays
-on the host in NumPy exactly as in the reference.  No CPU fallback: without the library or a GPU
-``update_posterior`` raises ``EngineUnavailableError``.
+on the host in NumPy exactly as in the reference.  ``pred_and_update_sequence`` predicts and learns a whole sample row by
+row on kernels of its own (``_mvnseq``, C ABI ``include/mvnseq.h``).  No CPU fallback: without the library or a GPU
+``update_posterior`` and ``pred_and_update_sequence`` raise ``EngineUnavailableError``.
 """
 from __future__ import annotations
 
@@ -120,6 +121,11 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._device = device
         self._engine = None
         self._data_pass_factory = None       # test seam only (tests/fake_engine.py); the default is the HIP engine
+        self._seq_engine = None
+        self._mvnseq_pass_factory = None     # test seam only (tests/mvn_seq_oracle.py)
+        # the traces of pred_and_update_sequence: name -> ndarray, or a device tensor fetched on first read
+        self._seq = {"means": None, "logdet": np.zeros(0), "quad": np.zeros(0)}
+        self.p_nus = np.zeros(0)
         self.h0_m_vec = np.zeros(D)
         self.h0_kappa = 1.0
         self.h0_nu = float(D)
@@ -135,6 +141,33 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.p_v_mat = np.eye(D) / 2.0
         self.p_v_mat_inv = np.eye(D) * 2.0
         self.set_h0_params(h0_m_vec, h0_kappa, h0_nu, h0_w_mat)
+
+    def _fetch(self, name):
+        """A trace of ``pred_and_update_sequence`` as a float64 ndarray (None if the call did not produce it): it stays on
+        the device until the first read."""
+        a = self._seq[name]
+        if isinstance(a, torch.Tensor):
+            a = self._seq[name] = a.detach().to("cpu").double().numpy()
+        return a
+
+    @property
+    def p_m_vecs(self):
+        return self._fetch("means")
+
+    @property
+    def p_v_logdets(self):
+        return self._fetch("logdet")
+
+    @property
+    def p_quads(self):
+        return self._fetch("quad")
+
+    def __getstate__(self):
+        for name in self._seq:
+            self._fetch(name)
+        state = dict(self.__dict__)
+        state["_seq_engine"] = None
+        return state
 
     def get_constants(self):
         return {"c_degree": self.c_degree}
@@ -158,9 +191,8 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         return {"hn_m_vec": self.hn_m_vec, "hn_kappa": self.hn_kappa, "hn_nu": self.hn_nu, "hn_w_mat": self.hn_w_mat}
 
     # ------------------------------------------------------------------ the data pass
-    def _moments(self, x):
-        """(n, x_bar [D], scatter [D, D] = sum (x - x_bar)(x - x_bar)^T) of the rows of x, from ONE pass of the GMM
-        M-step kernel with K = 1 and unit responsibilities (no E-step, nothing N-sized on the host)."""
+    def _check_sample(self, x):
+        """The rows [n, D] of a sample, accepted and refused as the reference does it (ref:494-499)."""
         D = self.c_degree
         if isinstance(x, torch.Tensor):
             if not (x.dtype.is_floating_point and x.dim() >= 1):
@@ -169,7 +201,13 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
             _check.float_vecs(x, "x", DataFormatError)
         if x.shape[-1] != D:
             raise DataFormatError(f"x.shape[-1] must be c_degree:{D}")
-        x = x.reshape(-1, D)
+        return x.reshape(-1, D)
+
+    def _moments(self, x):
+        """(n, x_bar [D], scatter [D, D] = sum (x - x_bar)(x - x_bar)^T) of the rows of x, from ONE pass of the GMM
+        M-step kernel with K = 1 and unit responsibilities (no E-step, nothing N-sized on the host)."""
+        D = self.c_degree
+        x = self._check_sample(x)
         n = x.shape[0]
         if self._data_pass_factory is not None:
             eng = self._data_pass_factory(1, D, x)
@@ -278,6 +316,65 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         prediction = self.make_prediction(loss=loss)
         self.update_posterior(x[np.newaxis, :])
         return prediction
+
+    def pred_and_update_sequence(self, x, loss="squared", *, code_length=False, chunk_bytes=None):
+        """``[pred_and_update(x[i], loss) for i in range(n)]`` over the rows of ``update_posterior(x)``, in order, in one
+        device pass (``_mvnseq.MvnSeqPass``, DESIGN.md 4f "Sequential prediction, multivariate normal"): prediction i is
+        made from the posterior of the rows before i, then row i is learnt.
+
+        ``x`` is accepted and refused as ``update_posterior`` does it (NumPy or torch, f32 or f64, a device tensor is read
+        where it lies, rows may be strided); a refused sample changes nothing.  The return is the float64 ``[n, D]``
+        predictive means for ``loss`` "squared" and "0-1" - a NumPy array for NumPy input, a tensor on the model's device
+        otherwise.  With ``code_length=True`` it is ``(means, nats)``, ``nats[i] = -ln p(x[i] | rows before i)`` float64
+        ``[n]``; ``loss=None`` needs ``code_length=True`` and returns ``nats`` alone.  "KL" is refused: a frozen
+        ``scipy.stats.multivariate_t`` holds one parameter set, not n.
+
+        Afterwards ``p_m_vecs`` [n, D], ``p_nus`` [n], ``p_v_logdets`` [n] (ln det p_v_mat of row i) and ``p_quads`` [n]
+        ((x_i - p_m_i)^T p_v_mat_i (x_i - p_m_i)) hold the n sequential parameter sets; the per-row ``p_v_mat`` is not
+        produced (n D^2 doubles).  Under ``loss=None`` no [n, D] array is made at all and ``p_m_vecs`` is None.  ``hn_*``
+        are bit for bit what ``update_posterior(x)`` leaves: the method ends with that very call on the same tensor and
+        with ``calc_pred_dist()``, so ``p_m_vec`` / ``p_nu`` / ``p_v_mat`` describe the NEXT point - the one difference
+        from the row loop, which leaves the last row's predictive there.  ``chunk_bytes`` bounds the workspace (default
+        256 MiB): ``_mvnseq.plan_blocks(...)`` blocks go into one pass, and the cut does not change a bit of the result."""
+        if loss == "KL":
+            raise CriteriaError("\"KL\" is not supported for a sequence: scipy.stats.multivariate_t cannot hold n parameter "
+                                "sets. The n parameter sets are in p_m_vecs, p_nus, p_v_logdets and p_quads after a call "
+                                "with another loss.")
+        if loss is None:
+            if not code_length:
+                raise CriteriaError("loss=None returns the code lengths alone: pass code_length=True with it.")
+        elif not (isinstance(loss, str) and loss in ("squared", "0-1")):
+            raise CriteriaError("Unsupported loss function! "
+                                "This function supports \"squared\", \"0-1\", and \"KL\".")
+        as_numpy = not isinstance(x, torch.Tensor)
+        x = self._check_sample(x)
+        n, D = x.shape[0], self.c_degree
+        want = (("means",) if loss is not None else ()) + ("logdet", "quad") + (("nats",) if code_length else ())
+        nu0 = float(self.hn_nu)
+        if n > 0:
+            if self._mvnseq_pass_factory is not None:
+                eng = self._mvnseq_pass_factory(D)
+            else:
+                if self._seq_engine is None:
+                    from .._mvnseq import MvnSeqPass
+                    self._seq_engine = MvnSeqPass(D, self._device)
+                eng = self._seq_engine
+            from .._mvnseq import start_state
+            xd = eng.adopt(x)
+            out = eng.run(xd, start_state(self.hn_w_mat_inv, self.hn_m_vec, self.hn_kappa, self.hn_nu), want, chunk_bytes)
+            self.update_posterior(xd)
+            self.calc_pred_dist()
+        else:                    # no rows: nothing to predict, nothing to learn, nothing to launch
+            out = {k: torch.zeros((0, D) if k == "means" else 0, dtype=torch.float64) for k in want}
+        self._seq = {k: out.get(k) for k in ("means", "logdet", "quad")}
+        self.p_nus = nu0 + np.arange(n) - D + 1
+        nats = out.get("nats")
+        if code_length and as_numpy:
+            nats = nats.detach().to("cpu").numpy()
+        if loss is None:
+            return nats
+        means = self.p_m_vecs if as_numpy else out["means"]
+        return (means, nats) if code_length else means
 
     def fit(self, x):
         self.reset_hn_params()
