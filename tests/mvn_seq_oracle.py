@@ -12,6 +12,7 @@
 * ``log_marginal``: ln p(X) of a sample between two states, for the sum of the code lengths.
 * ``CpuMvnSeqPass``: CPU stand-in for ``bayesml_amd._mvnseq.MvnSeqPass`` behind the private
   ``LearnModel._mvnseq_pass_factory`` seam; the product path never constructs it.
+* ``sweep`` / ``synth`` / ``model`` / ``budget_for``: what the GPU tests share (``sweep`` also runs on the stand-in).
 """
 import numpy as np
 import torch
@@ -172,31 +173,38 @@ def block_form(x, start, blocks_per_pass=None, dd_threshold=DD_THRESHOLD, diag=N
 
 
 # ---- the loops ---------------------------------------------------------------------------------------------------------------
-def row_loop(x, m, kappa, nu, w_inv):
+def row_loop(x, m, kappa, nu, w_inv, rows=None):
     """The reference's loop in float64 (bayesml/multivariate_normal/_multivariatenormal.py: calc_pred_dist :687-693,
     make_prediction's multivariate_t, update_posterior :501-524 with one row, its ``inv`` included):
-    (p_m_vecs, p_nus, p_v_logdets, p_quads, nats, final state (m, kappa, nu, w_inv))."""
+    (p_m_vecs, p_nus, p_v_logdets, p_quads, nats, final state (m, kappa, nu, w_inv)).  ``rows``: the rows to predict (all
+    if None); the state is updated at every row - that recursion does not read the inverse - and the predicted rows'
+    outputs are the full loop's bits, the others' p_v_logdets, p_quads and nats NaN."""
     from scipy.stats import multivariate_t
     x = np.asarray(x, dtype=np.float64)
     n, D = x.shape
     m, w_inv = np.array(m, dtype=np.float64), np.array(w_inv, dtype=np.float64)
     kappa, nu = float(kappa), float(nu)
-    w = np.linalg.inv(w_inv)
-    means, p_nus, logdets, quads, nats = np.zeros((n, D)), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    wanted = np.ones(n, dtype=bool)
+    if rows is not None:
+        wanted[:] = False
+        wanted[np.asarray(rows, dtype=np.int64)] = True
+    means, p_nus = np.zeros((n, D)), np.zeros(n)
+    logdets, quads, nats = (np.full(n, np.nan) for _ in range(3))
     for i in range(n):
         p_nu = nu - D + 1
-        p_v = kappa * p_nu / (kappa + 1) * w
-        p_v_inv = (kappa + 1) / kappa / p_nu * w_inv
         means[i], p_nus[i] = m, p_nu
-        logdets[i] = np.linalg.slogdet(p_v)[1]
         diff = x[i] - m
-        quads[i] = diff @ p_v @ diff
-        nats[i] = -multivariate_t.logpdf(x[i], loc=m, shape=p_v_inv, df=p_nu)
+        if wanted[i]:
+            w = np.linalg.inv(w_inv)
+            p_v = kappa * p_nu / (kappa + 1) * w
+            p_v_inv = (kappa + 1) / kappa / p_nu * w_inv
+            logdets[i] = np.linalg.slogdet(p_v)[1]
+            quads[i] = diff @ p_v @ diff
+            nats[i] = -multivariate_t.logpdf(x[i], loc=m, shape=p_v_inv, df=p_nu)
         w_inv = w_inv + diff[:, None] @ diff[None, :] * kappa / (kappa + 1)          # (x_bar = x_i, the scatter is zero)
         m = (kappa * m + x[i]) / (kappa + 1)
         kappa += 1
         nu += 1
-        w = np.linalg.inv(w_inv)
     return means, p_nus, logdets, quads, nats, (m, kappa, nu, w_inv)
 
 
@@ -376,3 +384,79 @@ def model_at(D, start, device=None):
 
 def hn_equal(a, b):
     return all(np.array_equal(getattr(a, k), getattr(b, k)) for k in HN)
+
+
+# ---- the models on the device (the GPU tests' helpers) ----------------------------------------------------------------------
+def dev():
+    return torch.device("cuda", 0)
+
+
+def model(D, start=None):
+    return model_at(D, start, device=dev())
+
+
+def default_start(D):
+    return (np.zeros(D), 1.0, float(D), np.eye(D))
+
+
+def outputs(m, nats):
+    return (m.p_m_vecs, m.p_v_logdets, m.p_quads, nats)
+
+
+def sweep(label, D, ns, x, start, rows=None, make_model=None):
+    """Every n of ``ns`` is a call on the first n rows; the loops run once, on the longest: prediction i does not depend on
+    the rows after i.  ``rows``: the rows the long-double loop predicts and the comparison looks at (all if None).
+    ``make_model``: (D, start) -> a model at that state; the device's ``model`` if None, ``model_at`` for the CPU stand-in."""
+    make = model if make_model is None else make_model
+    exact = pick(ld_row_loop(x, *start, rows=rows))
+    ref = pick(row_loop(x, *start, rows=rows))
+    worst = 0.0
+    for n in ns:
+        m = make(D, start)
+        means, nats = m.pred_and_update_sequence(x[:n], code_length=True)
+        got = outputs(m, nats)
+        assert means.shape == (n, D) and all(a.shape == (n,) for a in got[1:]) and m.p_nus.shape == (n,)
+        assert np.array_equal(m.p_nus, start[2] + np.arange(n) - D + 1)
+        sub = None if rows is None else [i for i in rows if i < n]
+        worst = max(worst, check(f"{label} n = {n}", got, [e[:n] for e in exact], [r[:n] for r in ref], x[:n], D, rows=sub))
+        u = make(D, start).update_posterior(x[:n])
+        assert hn_equal(m, u)
+        u.calc_pred_dist()
+        assert np.array_equal(m.p_m_vec, u.p_m_vec) and m.p_nu == u.p_nu and np.array_equal(m.p_v_mat, u.p_v_mat)
+    print(f"{label}: worst error / tolerance {worst:.2f}")
+    return worst
+
+
+def second_call(label, D, x, start, n1, make_model=None):
+    """Rows [0, n1) in one call and the rest in a second on the same model: the second call's pivot is its own row 0, and
+    its start is whatever the first left.  The oracle starts from the model's own hn_* after the first call; hn_* after both
+    and the next-point predictive are update_posterior's on the two pieces."""
+    make = model if make_model is None else make_model
+    m = make(D, start)
+    m.pred_and_update_sequence(x[:n1])
+    mid = (m.hn_m_vec.copy(), float(m.hn_kappa), float(m.hn_nu), m.hn_w_mat_inv.copy())
+    x2 = x[n1:]
+    n2 = len(x2)
+    means, nats = m.pred_and_update_sequence(x2, code_length=True)
+    got = outputs(m, nats)
+    assert means.shape == (n2, D) and all(a.shape == (n2,) for a in got[1:])
+    assert np.array_equal(m.p_nus, mid[2] + np.arange(n2) - D + 1)
+    worst = check(label, got, pick(ld_row_loop(x2, *mid)), pick(row_loop(x2, *mid)), x2, D)
+    u = make(D, start).update_posterior(x[:n1]).update_posterior(x2)
+    assert hn_equal(m, u)
+    u.calc_pred_dist()
+    assert np.array_equal(m.p_m_vec, u.p_m_vec) and m.p_nu == u.p_nu and np.array_equal(m.p_v_mat, u.p_v_mat)
+    print(f"{label}: worst error / tolerance {worst:.2f}")
+    return worst
+
+
+def synth(D, n, seed, loc=0.7, spread=1.0):
+    rng = np.random.default_rng(seed)
+    mix = rng.standard_normal((D, D)) / np.sqrt(D) + np.eye(D)
+    return loc + spread * (rng.standard_normal((n, D)) @ mix.T)
+
+
+def budget_for(D, blocks):
+    """chunk_bytes that makes a pass hold so many blocks."""
+    from bayesml_amd import _mvnseq
+    return 8 * _mvnseq.work_slots(D, blocks)

@@ -11,53 +11,10 @@ import torch
 
 import mvn_seq_oracle as seq
 from conftest import load_golden
+from mvn_seq_oracle import budget_for, default_start, dev, model, outputs, sweep, synth
 
 pytestmark = pytest.mark.gpu
 B = seq.BLOCK
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def model(D, start=None):
-    return seq.model_at(D, start, device=dev())
-
-
-def default_start(D):
-    return (np.zeros(D), 1.0, float(D), np.eye(D))
-
-
-def outputs(m, nats):
-    return (m.p_m_vecs, m.p_v_logdets, m.p_quads, nats)
-
-
-def sweep(label, D, ns, x, start, rows=None):
-    """Every n of ``ns`` is a call on the first n rows; the loops run once, on the longest: prediction i does not depend on
-    the rows after i.  ``rows``: the rows the long-double loop predicts and the comparison looks at (all if None)."""
-    exact = seq.pick(seq.ld_row_loop(x, *start, rows=rows))
-    ref = seq.pick(seq.row_loop(x, *start))
-    worst = 0.0
-    for n in ns:
-        m = model(D, start)
-        means, nats = m.pred_and_update_sequence(x[:n], code_length=True)
-        got = outputs(m, nats)
-        assert means.shape == (n, D) and all(a.shape == (n,) for a in got[1:]) and m.p_nus.shape == (n,)
-        assert np.array_equal(m.p_nus, start[2] + np.arange(n) - D + 1)
-        sub = None if rows is None else [i for i in rows if i < n]
-        worst = max(worst, seq.check(f"{label} n = {n}", got, [e[:n] for e in exact], [r[:n] for r in ref], x[:n], D, rows=sub))
-        u = model(D, start).update_posterior(x[:n])
-        assert seq.hn_equal(m, u)
-        u.calc_pred_dist()
-        assert np.array_equal(m.p_m_vec, u.p_m_vec) and m.p_nu == u.p_nu and np.array_equal(m.p_v_mat, u.p_v_mat)
-    print(f"{label}: worst error / tolerance {worst:.2f}")
-    return worst
-
-
-def synth(D, n, seed, loc=0.7, spread=1.0):
-    rng = np.random.default_rng(seed)
-    mix = rng.standard_normal((D, D)) / np.sqrt(D) + np.eye(D)
-    return loc + spread * (rng.standard_normal((n, D)) @ mix.T)
 
 
 @pytest.mark.parametrize("name", seq.FIXTURES)
@@ -100,11 +57,6 @@ def test_hard_cases(case):
         x = synth(D, n, 502)
         x[:100, 3] = x[0, 3]
     sweep(case, D, (n,), x, start)
-
-
-def budget_for(D, blocks):
-    from bayesml_amd import _mvnseq
-    return 8 * _mvnseq.work_slots(D, blocks)
 
 
 def test_passes_are_bit_equal_to_one_call():
