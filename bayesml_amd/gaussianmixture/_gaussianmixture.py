@@ -18,7 +18,7 @@ import warnings
 import numpy as np
 import torch
 
-from .. import _check, _kside, base
+from .. import _check, _kside, _stmix, base
 from . import _small
 from .._device import DeviceModel
 from .._dist import SingleProcess
@@ -197,6 +197,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
     """
 
     _row_tiling = True
+    _stmix_pass_factory = None          # private test seam (tests/stmix_oracle.py)
 
     def __init__(self, c_num_classes, c_degree, h0_alpha_vec=None, h0_m_vecs=None, h0_kappas=None,
                  h0_nus=None, h0_w_mats=None, seed=None, *, device=None, comm=None, verbose=True):
@@ -633,6 +634,30 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self.p_nus[:] = self.hn_nus - self.c_degree + 1
         self.p_lambda_mats[:] = (self.hn_kappas * self.p_nus / (self.hn_kappas + 1))[:, np.newaxis, np.newaxis] * self.hn_w_mats
         return self
+
+    def calc_pred_logpdf(self, x, *, assign=False):
+        """``ln p(x_i | data)`` of the rows of ``x`` under the predictive Student-t mixture, float64 ``[N]``, in one device
+        pass (``_stmix.StudentMixturePass``, DESIGN.md "Predictive log-density of a sample"): held-out log-likelihood,
+        anomaly scores.  ``assign=True`` returns ``(lnp, z)`` with ``z`` int64 ``[N]``, the component with the largest
+        ``pi_k St(x_i | mu_k, Lambda_k, nu_k)`` (the lowest index on a tie): hard assignments under the predictive.
+
+        ``x`` is accepted and refused as ``update_posterior`` does it (NumPy or torch, f32 or f64, a device tensor is read
+        where it lies, rows may be strided; a single ``[D]`` vector is one row); a refused sample changes nothing.  The
+        results are NumPy arrays for a NumPy ``x`` and tensors on the model's device otherwise.  ``calc_pred_dist()`` runs
+        first, so ``p_*`` are those of the current ``hn_*``; nothing else changes - ``hn_*``, ``r_vecs`` and an open fit
+        engine stay as they were, and no fit workspace is created."""
+        as_numpy = not isinstance(x, torch.Tensor)
+        x = self._check_rows(x)
+        self.calc_pred_dist()
+
+        def params(dev):
+            t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)   # noqa: E731
+            # Lambda_k = s_k W_k with W_k^-1 = G G^T: U_k = sqrt(s_k) G^-1 (the K-side's factor, rescaled)
+            scale = self.hn_kappas * self.p_nus / (self.hn_kappas + 1)
+            u = torch.sqrt(t(scale))[:, None, None] * _stmix.precision_factor(t(self.hn_w_mats_inv))
+            return t(self.p_pi_vec), t(self.p_mu_vecs), t(self.p_nus), u
+
+        return _stmix.model_logpdf(self, "gaussianmixture", x, as_numpy, self.c_num_classes, params, bool(assign))
 
     def make_prediction(self, loss="squared"):
         """Predicted next point: mixture mean ("squared") or the highest weighted mode ("0-1") (ref:1072-1102)."""

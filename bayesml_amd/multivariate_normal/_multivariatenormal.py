@@ -16,7 +16,7 @@ import warnings
 import numpy as np
 import torch
 
-from .. import _check, base
+from .. import _check, _stmix, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError, ResultWarning
 
 _PLOT_MSG = "if c_degree > 2, it is impossible to visualize the model by this function."
@@ -112,6 +112,8 @@ class GenModel(base.Generative):
 class LearnModel(base.Posterior, base.PredictiveMixin):
     """Posterior and predictive distribution (ref:281-800).  Positional parameters are the reference's:
     ``c_degree, h0_m_vec=None, h0_kappa=1.0, h0_nu=None, h0_w_mat=None``; keyword-only ``device`` selects the GPU."""
+
+    _stmix_pass_factory = None          # private test seam (tests/stmix_oracle.py)
 
     def __init__(self, c_degree, h0_m_vec=None, h0_kappa=1.0, h0_nu=None, h0_w_mat=None, *, device=None):
         self.c_degree = _check.pos_int(c_degree, "c_degree", ParameterFormatError)
@@ -297,6 +299,24 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.p_v_mat[:] = self.hn_kappa * self.p_nu / (self.hn_kappa + 1) * self.hn_w_mat
         self.p_v_mat_inv[:] = (self.hn_kappa + 1) / self.hn_kappa / self.p_nu * self.hn_w_mat_inv
         return self
+
+    def calc_pred_logpdf(self, x):
+        """``ln St(x_i | p_m_vec, p_v_mat, p_nu)`` of the rows of ``x`` under the predictive distribution, float64 ``[N]``, in
+        one device pass: the one-component case of ``gaussianmixture.LearnModel.calc_pred_logpdf`` on the same engine
+        (``_stmix.StudentMixturePass``).  ``x`` is accepted and refused as ``update_posterior`` does it (a single ``[D]``
+        vector is one row); the result is a NumPy array for a NumPy ``x`` and a tensor on the model's device otherwise.
+        ``calc_pred_dist()`` runs first; ``hn_*`` and the traces of ``pred_and_update_sequence`` stay as they were."""
+        as_numpy = not isinstance(x, torch.Tensor)
+        x = self._check_sample(x)
+        self.calc_pred_dist()
+
+        def params(dev):
+            t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)   # noqa: E731
+            # p_v_mat^-1 = G G^T: U = G^-1, U^T U = p_v_mat
+            return (torch.ones(1, dtype=torch.float64, device=dev), t(self.p_m_vec)[None, :], t([float(self.p_nu)]),
+                    _stmix.precision_factor(t(self.p_v_mat_inv)[None, :, :]))
+
+        return _stmix.model_logpdf(self, "multivariate_normal", x, as_numpy, 1, params, False)
 
     def make_prediction(self, loss="squared"):
         if loss in ("squared", "0-1"):
