@@ -190,6 +190,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self.rng = np.random.default_rng(seed)
         self._device, self._comm, self._verbose = device, SingleProcess(), verbose
         self._data_pass_factory = None          # test seam only (see gaussianmixture.LearnModel)
+        self._hmmpred_pass_factory = None       # test seam only: (K, D) -> a stand-in for _hmmpred.HmmFilterPass
         self._engine = self._x_dev = self._r_cache = None
         K, D = self.c_num_classes, self.c_degree
         (self.h0_eta_vec, self.h0_zeta_vecs, self.h0_m_vecs, self.h0_kappas, self.h0_nus, self.h0_w_mats) = _defaults(K, D)
@@ -519,6 +520,42 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self.p_nus[:] = self.hn_nus - self.c_degree + 1
         self.p_lambda_mats[:] = (self.hn_kappas * self.p_nus / (self.hn_kappas + 1))[:, np.newaxis, np.newaxis] * self.hn_w_mats
         return self
+
+    def calc_pred_logpdf(self, x, *, start="last", assign=False, return_state=False, chunk_bytes=None):
+        """``ln p(x_t | x_0 .. x_{t-1}, data)`` of the rows of the sequence ``x`` under the predictive HMM - transitions
+        ``p_a_mat``, Student-t emissions ``St(mu_k = p_mu_vecs, Lambda_k = p_lambda_mats, nu_k = p_nus)`` - float64 ``[T]``,
+        in one device pass (``_hmmpred.HmmFilterPass``, DESIGN.md "Predictive log-density of a sequence").  The sum is the
+        log predictive of the sequence: held-out log-likelihood; the entries are per-step anomaly scores.
+
+        ``start`` is the state distribution of row 0: ``"last"`` = ``gamma_vecs[-1] @ p_a_mat``, the continuation of the
+        learnt sequence (the weights ``make_prediction`` uses); ``"initial"`` = ``hn_eta_vec / hn_eta_vec.sum()``, a fresh
+        sequence; or a vector of ``c_num_classes`` non-negative weights summing to 1 within 1e-12.  Anything else raises
+        ``ParameterFormatError``.  ``assign=True`` adds ``z`` int64 ``[T]``, the state with the largest filtered posterior
+        ``phi_t = p(z_t | x_0 .. x_t)`` (the lowest index on a tie); ``return_state=True`` adds ``phi_{T-1}`` ``[K]``, and
+        ``start = state @ model.p_a_mat`` in the next call continues the stream where this one ended (for ``T = 0`` the
+        state returned is the start vector itself: nothing was filtered).
+
+        ``x`` is accepted and refused as ``update_posterior`` does it (NumPy or torch, f32 or f64, a device tensor is read
+        where it lies, rows may be strided; a single ``[D]`` vector is one row); a refused sample changes nothing.  The
+        results are NumPy arrays for a NumPy ``x`` and tensors on the model's device otherwise.  ``chunk_bytes`` (default
+        1 GiB) bounds the scratch: a longer sequence goes through in time slices, each started from the true ``phi A`` of
+        the slice before; the input is not copied.  ``calc_pred_dist()`` runs first; nothing of the fit changes - ``hn_*``,
+        ``gamma_vecs``, the statistics and an open fit engine stay as they were, and no fit workspace is created.  Up to 64
+        states the recursion runs chunk-parallel, up to 256 as one serial walk; more raise ``EngineLimitError``."""
+        from .. import _hmmpred, _stmix
+        as_numpy = not isinstance(x, torch.Tensor)
+        x = self._check_rows(x)
+        _hmmpred.start_vector(self, start)          # (refused before anything changes)
+        self.calc_pred_dist()
+
+        def params(dev):
+            t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)   # noqa: E731
+            # Lambda_k = s_k W_k with W_k^-1 = G G^T: U_k = sqrt(s_k) G^-1 (the K-side's factor, rescaled)
+            scale = self.hn_kappas * self.p_nus / (self.hn_kappas + 1)
+            u = torch.sqrt(t(scale))[:, None, None] * _stmix.precision_factor(t(self.hn_w_mats_inv))
+            return t(self.p_a_mat), t(self.p_mu_vecs), t(self.p_nus), u
+
+        return _hmmpred.model_logpdf(self, x, as_numpy, start, bool(assign), bool(return_state), chunk_bytes, params)
 
     def make_prediction(self, loss="squared"):
         """Next-observation prediction from ``gamma_vecs[-1] @ p_a_mat`` (ref:1340-1370)."""
