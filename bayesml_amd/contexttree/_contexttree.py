@@ -6,7 +6,8 @@ the posterior lives in dense per-level tables on the device (``_ctree.CtreePass`
 form of DESIGN.md "Context tree": ``ctree_count`` counts every (context, symbol) pair of the sample where it lies, one host
 read of ``[n | bad]`` decides whether the sample is accepted, and ``ctree_sweep`` applies the update level by level.
 ``estimate_params`` runs ``ctree_map`` and builds only the pruned MAP tree.  ``pred_and_update_sequence`` is the per-symbol
-loop of ``pred_and_update`` over a whole sample in its level-wise form (``_ctseq.SequencePass``).  What touches one root-to-leaf path
+loop of ``pred_and_update`` over a whole sample in its level-wise form (``_ctseq.SequencePass``); ``calc_pred_logpdf`` scores a
+held-out sample under the posterior as it stands, every position at once (``_ctpred.PredPass``).  What touches one root-to-leaf path
 (``calc_pred_dist``, ``pred_and_update``) gathers its D + 1 rows and works on the host.  ``hn_root`` is a property that
 materialises the ``_Node`` tree from the tables on demand; a tree given to a setter is scattered into them.
 
@@ -20,7 +21,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .. import _check, _ctree, _ctseq, base
+from .. import _check, _ctpred, _ctree, _ctseq, base
 from . import _nodes
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError
 
@@ -210,7 +211,9 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
 
     _ctree_pass_factory = None        # private test seam (tests/fake_contexttree_engine.py)
     _ctseq_pass_factory = None        # private test seam (tests/contexttree_seq_oracle.py)
+    _ctpred_pass_factory = None       # private test seam (tests/contexttree_pred_oracle.py)
     _seq_pass = None
+    _pred_pass = None
     _sparse = False                   # (a model pickled before the keyword existed is dense)
 
     def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, tables="dense", device=None):
@@ -249,6 +252,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
             state["_saved_tables"] = self._store.save(self._engine)
         state["_engine"] = None
         state.pop("_seq_pass", None)
+        state.pop("_pred_pass", None)
         state.pop("_store", None)           # (derived on loading: the state keeps the layout it always had)
         return state
 
@@ -316,15 +320,21 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         return {"hn_g": self.hn_g, "hn_beta_vec": self.hn_beta_vec, "hn_root": self.hn_root}
 
     # ---- learning ----------------------------------------------------------------------------------------------------------
-    def _adopt_sample(self, x):
-        """What ``update_posterior`` and ``pred_and_update_sequence`` accept as a sample, on the engine's device."""
+    @staticmethod
+    def _check_sample(x):
+        """The host half of ``_adopt_sample``: the sample as an array or tensor of a kind the engine adopts."""
         if _check._is_int(x) and x >= 0:
             x = np.asarray([x])
         if _check.sample_kind(x) != "i":
             raise DataFormatError("x" + _check.SAMPLE_MSG["nonneg_ints"])
         if (x.numel() if hasattr(x, "numel") else x.size) == 0:
             np.max(np.zeros(0))          # the reference's x.max() of an empty sample: ValueError
-        return self._eng().adopt(x)
+        return x
+
+    def _adopt_sample(self, x):
+        """What ``update_posterior``, ``pred_and_update_sequence`` and ``calc_pred_logpdf`` accept as a sample, on the
+        engine's device."""
+        return self._eng().adopt(self._check_sample(x))
 
     def _refuse_bad_symbols(self, xd, bad):
         """``bad`` symbols were counted outside 0..c_k-1: the reference's message for a negative one, else for a large one."""
@@ -389,6 +399,64 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.p_theta_vec[:] = p
         self._eng().scatter(idx, g, beta, np.ones(len(idx), np.uint8), leaf)
         return self
+
+    @staticmethod
+    def _sequence_offsets(lengths, n):
+        """``lengths`` as the S + 1 starts of the sequences of a sample of n symbols (host int64), checked on the host."""
+        msg = ("lengths must be a 1-dimensional array, tensor or list of non-negative integers whose sum is the length "
+               "of x")
+        if hasattr(lengths, "detach"):
+            lengths = lengths.detach().cpu().numpy()
+        try:
+            arr = np.asarray(lengths)
+        except Exception:
+            raise DataFormatError(msg) from None
+        if isinstance(lengths, (list, tuple)) and arr.size == 0:
+            arr = arr.astype(np.int64)
+        if arr.ndim != 1 or arr.dtype.kind not in "iu" or (arr.size and int(arr.min()) < 0):
+            raise DataFormatError(msg)
+        off = np.concatenate([[0], np.cumsum(arr.astype(np.int64))]).astype(np.int64)
+        if int(off[-1]) != n:
+            raise DataFormatError(msg)
+        return off
+
+    def calc_pred_logpdf(self, x, *, lengths=None, assign=False, return_dist=False, totals=False):
+        """``ln p(x[i] | x[i-1], ..., x[i-min(i, c_d_max)], data)`` of every position of a held-out sample under the
+        posterior as it stands, float64 ``[n]``, in one device pass (``_ctpred.PredPass``, DESIGN.md "Predictive
+        log-probability of held-out sequences"): the logarithm of entry ``x[i]`` of what ``calc_pred_dist(x[:i + 1])``
+        leaves in ``p_theta_vec`` (ref:954-989).  ``-lnp.sum()`` is the code length of the sample in nats.
+
+        ``x`` is accepted and refused as ``update_posterior`` does it.  ``lengths`` (1-D non-negative integers summing to
+        ``n``) makes ``x`` the concatenation of independent sequences: no context reaches before the start of its own
+        sequence.  ``assign=True`` adds ``z``, int64 ``[n]``, the first maximum of each position's predictive vector
+        (``make_prediction(loss="0-1")``); ``return_dist=True`` adds the vectors, float64 ``[n, c_k]``; ``totals=True``
+        (needs ``lengths``) adds the sum of ``lnp`` over each sequence, float64 ``[S]``, 0.0 for an empty one, by a
+        fixed-tree reduction that gives the same bits on every run.  With flags the return is the tuple
+        ``(lnp, z, dist, totals)`` without the parts not asked for: NumPy arrays for a NumPy ``x``, tensors on the model's
+        device otherwise.
+
+        Nothing is learnt and nothing changes: unlike the reference's ``calc_pred_dist``, no default-valued node is
+        appended to the tree (such a node predicts exactly what its absence predicts), and ``hn_*``, ``p_theta_vec`` and
+        the tables stay as they were.  Dense and sparse tables of the same tree give the same bits.  No CPU fallback."""
+        if totals and lengths is None:
+            raise ParameterFormatError("totals=True sums over the sequences that lengths describes: pass lengths with it.")
+        x = self._check_sample(x)
+        as_numpy = not hasattr(x, "numel")
+        seq_off = None
+        if lengths is not None:
+            seq_off = self._sequence_offsets(lengths, int(x.numel() if hasattr(x, "numel") else x.size))
+        eng = self._eng()
+        xd = eng.adopt(x)
+        if self._pred_pass is None:
+            make = self._ctpred_pass_factory
+            self._pred_pass = make(eng, self._store) if make is not None else _ctpred.PredPass(eng, self._store)
+        bad, lnp, z, dist, tot = self._pred_pass.run(xd, seq_off, self._has_root, self.hn_g, self.hn_beta_vec,
+                                                     assign=bool(assign), dist=bool(return_dist), totals=bool(totals))
+        self._refuse_bad_symbols(xd, bad)
+        out = [v for v in (lnp, z, dist, tot) if v is not None]
+        if as_numpy:
+            out = [v.cpu().numpy() for v in out]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def make_prediction(self, loss="KL"):
         if loss == "KL":

@@ -150,6 +150,10 @@ class DenseStore(_Store):
     def restore(self, eng, saved):
         eng.set_tables(saved)
 
+    def pred_tables(self, eng):
+        """What ``_ctpred.PredPass`` reads: the device tensors and the first slot of every level."""
+        return dict(beta=eng.beta, g=eng.g, exists=eng.exists, off=self.off)
+
 
 class SparseStore(_Store):
     """``_ctsp.SparseCtreePass``: the key packs the context, ``_ctsp.symbol_bits(k)`` bits per symbol from the top."""
@@ -178,6 +182,10 @@ class SparseStore(_Store):
 
     def restore(self, eng, saved):
         eng.set_nodes(saved)
+
+    def pred_tables(self, eng):
+        """As ``DenseStore.pred_tables``, with the keys; ``off`` holds the capacities as they are now."""
+        return dict(beta=eng.beta, g=eng.g, exists=eng.exists, off=list(eng.off), key=eng.key)
 
 
 def store_for(sparse, k, D):
