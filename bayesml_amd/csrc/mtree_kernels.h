@@ -16,19 +16,12 @@
 #include <stdint.h>
 
 #include "../../include/mtree.h"
+#include "mtree_common.h"
 
 namespace mtree {
 
 constexpr int kThreads = 256;
-constexpr int kWave = 64;
 
-struct Forest {        // mtree_forest by value
-    int n_trees, n_nodes, n_thr, max_depth, dim_cont, dim_cat;
-    const int32_t *tree_off, *feat, *child0, *nchild, *thr_off, *depth;
-    const double* thr;
-};
-
-__device__ __attribute__((noinline)) double lgamma_call(double x) { return lgamma(x); }
 
 // The child of node v (table index) that row i goes to, or -1 where the walk stops.  [lo, hi) is the tree's node range.
 template <typename TC, typename TK>

@@ -24,14 +24,9 @@ namespace mtree {
 using gmmvb::d4;
 using gmmvb::mfma_f64;
 
-constexpr int kLrD = MTREE_LR_MAX_DEGREE;
-constexpr int kLrTri = kLrD * (kLrD + 1) / 2;
 constexpr int kLrQuads = 8;       // quads (of four rows) whose loads a lane has in flight before the first MFMA
 constexpr double kLn2Pi = 1.8378770664093453;
 
-__host__ __device__ inline int lr_tri(int D) { return D * (D + 1) / 2; }
-// index of (i, j), i <= j, in the row-major upper triangle of a D x D matrix
-__device__ inline int lr_ut(int D, int i, int j) { return i * D - i * (i - 1) / 2 + (j - i); }
 // the same entry of the symmetric matrix for any (i, j)
 __device__ inline int lr_sym(int D, int i, int j) { return i <= j ? lr_ut(D, i, j) : lr_ut(D, j, i); }
 // index of (i, j), j <= i, in a row-major packed lower triangle
@@ -246,25 +241,6 @@ __global__ __launch_bounds__(kWave) void lr_fixup_kernel(int n_nodes, int nr, co
 }
 
 // ---- (g) ------------------------------------------------------------------------------------------------------------------
-// In place: the packed upper triangle A of a symmetric positive definite matrix becomes U with A = U'U (U upper, so
-// L = U').  Returns ln|A|.  A matrix that is not positive definite gives NaN, never a bad index.
-__device__ inline double lr_cholesky(double* A, int D) {
-    double lndet = 0.0;
-    for (int i = 0; i < D; ++i) {
-        double d = A[lr_ut(D, i, i)];
-        for (int k = 0; k < i; ++k) d -= A[lr_ut(D, k, i)] * A[lr_ut(D, k, i)];
-        d = sqrt(d);
-        A[lr_ut(D, i, i)] = d;
-        lndet += log(d);
-        for (int j = i + 1; j < D; ++j) {
-            double s = A[lr_ut(D, i, j)];
-            for (int k = 0; k < i; ++k) s -= A[lr_ut(D, k, i)] * A[lr_ut(D, k, j)];
-            A[lr_ut(D, i, j)] = s / d;
-        }
-    }
-    return 2.0 * lndet;
-}
-
 // One thread: out[0] = ln|Lambda_h0| of the prior vector h0 = [mu | upper triangle of Lambda | a | b | 0].
 __global__ void lr_prior_kernel(int D, const double* __restrict__ h0, double* __restrict__ out) {
     if (blockIdx.x != 0 || threadIdx.x != 0 || D < 1 || D > kLrD) return;

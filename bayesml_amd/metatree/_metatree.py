@@ -527,6 +527,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._h0 = None               # _Forest or None
         self._hn = None               # _Forest or None; while the engine lives, its state is the engine's
         self._p_x = None
+        self._pred_pass = None        # _mtpred.LogpdfPass on the current engine (calc_pred_logpdf)
         self._last_map = None
         self._mcmc_trace = None       # per step of the last MTMCMC / REMTMCMC fit: what mtgrow_accept returned, the exchanges
 
@@ -694,6 +695,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         if self._engine is not None:
             self._engine.close()
         self._engine = None
+        self._pred_pass = None
         self._hn = forest
 
     def _eng(self):
@@ -711,6 +713,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._hn_forest()
         state = dict(self.__dict__)
         state["_engine"] = None
+        state["_pred_pass"] = None
         state["_p_x"] = None
         state["SubModel"] = self.SubModel.__name__
         return state
@@ -1437,6 +1440,41 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
                     val[rows] = np.where(last, own, (1 - g) * own + g * val[rows])
             out += state["prob"][b] * val
         return out
+
+    def calc_pred_logpdf(self, x_continuous=None, x_categorical=None, y=None, *, total=False):
+        """ln p(y_i | x_i) of labelled rows under the fixed posterior forest, float64 [n], in one device pass
+        (``mtpred_logpdf``, include/mtpred.h; not in the reference): the logarithm of
+        ``calc_pred_dist(x).calc_pred_density(y)``, folded in the log domain, so a far-tail label gives a finite value where
+        the density underflows to 0.  ``total=True`` returns ``(lnp, sum of lnp)``, the sum formed on the device on a fixed
+        tree.  x is checked as ``calc_pred_dist`` checks it and y as ``update_posterior`` does; NumPy in gives NumPy out,
+        a tensor among the inputs gives tensors on the model's device.  Nothing is learnt and the rows kept by
+        ``calc_pred_dist`` stay as they are."""
+        if self._hn is None:
+            raise ParameterFormatError("the prediction needs a posterior forest: len(self.hn_metatree_list) must be > 0.")
+        xc, xk, n = self._check_sample_x(x_continuous, x_categorical)
+        self._check_values(xk)
+        y = self._check_sample_y(y, xc)
+        _check.shape_consistency(n, "x_continuous.shape[0] and x_categorical.shape[0]", y.shape[0], "y.shape[0]",
+                                 ParameterFormatError)
+        as_tensor = any(type(a) is not np.ndarray and hasattr(a, "data_ptr") for a in (x_continuous, x_categorical, y))
+        if n == 0:                        # nothing to score: no engine, no launch
+            if as_tensor:
+                import torch
+                lnp = torch.zeros(0, dtype=torch.float64, device=self._device or "cuda")
+            else:
+                lnp = np.zeros(0)
+            return (lnp, lnp.sum()) if total else lnp
+        eng = self._eng()
+        if self._pred_pass is None or self._pred_pass.eng is not eng:
+            from .. import _mtpred
+            self._pred_pass = _mtpred.LogpdfPass(eng)
+        xcd, xkd = eng.adopt_x(xc, xk)
+        lnp, tot = self._pred_pass.run(xcd, xkd, eng.adopt_y(y), total=total)
+        if not as_tensor:
+            lnp, tot = lnp.cpu().numpy(), (float(tot.cpu()[0]) if total else None)
+        elif total:
+            tot = tot[0]
+        return (lnp, tot) if total else lnp
 
     def calc_feature_importances(self):
         """ref:3452-3477 on the node tables."""
