@@ -6,6 +6,7 @@
 #include "../../include/hmmpred.h"
 #include "../../include/stmix.h"
 #include "entry.h"
+#include "hmmpred_emit.h"
 #include "hmmpred_kernels.h"
 
 #include <type_traits>
@@ -103,6 +104,32 @@ static int launch_emission_plain(const XT* x, const Args& a) {
     return g_err.launched("hmmpred emission_plain_kernel launch");
 }
 
+// hmmpred_emit.h: the per-row stage, shared with hmmbatch.hip (arguments checked by the caller)
+int emit_rows(int K, int D, int x_dtype, const void* x_dev, int64_t ldx, int64_t n_rows, const double* pivot_dev,
+              const double* img_dev, const double* c_dev, const double* nu_dev, double* lne, int64_t npad, double* rho,
+              double* m, hipStream_t st) {
+    const size_t esz = x_dtype == HMMPRED_F32 ? 4 : 8;
+    const int Kp = 16 * ((K + 15) / 16);
+    const Args a = {K, D, ldx, n_rows, pivot_dev, img_dev, c_dev, nu_dev, lne, npad, st};
+    int rc;
+    if (D > 128) {
+        rc = x_dtype == HMMPRED_F32 ? launch_emission_plain((const float*)x_dev, a) : launch_emission_plain((const double*)x_dev, a);
+    } else {
+        const bool vec = D % 16 == 0 && (uintptr_t)x_dev % (4 * esz) == 0 && ldx % 4 == 0;
+        rc = x_dtype == HMMPRED_F32 ? launch_emission((const float*)x_dev, vec, a) : launch_emission((const double*)x_dev, vec, a);
+    }
+    if (rc != HMMPRED_OK) return rc;
+    const unsigned pgrid = (unsigned)((n_rows + gmmvb::kPrepSteps - 1) / gmmvb::kPrepSteps);
+    if (K <= 64)
+        hipLaunchKernelGGL(gmmvb::hmm_prep_kernel, dim3(pgrid), dim3(256),
+                           ((size_t)Kp * (gmmvb::kPrepSteps + 1) + gmmvb::kPrepSteps) * sizeof(double), st, (const double*)lne, npad,
+                           n_rows, K, Kp, rho, m);
+    else
+        hipLaunchKernelGGL(gmmvb::hmm_prep_generic_kernel, dim3(pgrid), dim3(256), 0, st, (const double*)lne, npad, n_rows, K, Kp,
+                           rho, m);
+    return g_err.launched("hmmpred prep launch");
+}
+
 // sweep, replay and check of the chunk-parallel filter for KT blocks of 16 states
 template <int KT>
 static void launch_parallel(const double* rho, const double* a, int K, int64_t T, int64_t L, int64_t W, int64_t n_chunks,
@@ -182,24 +209,8 @@ int hmmpred_logpdf(int K, int D, int x_dtype, const void* x_dev, int64_t ldx, in
     if (W > L) W = L;
 
     // 1. emission: ln e component-major, then rho' (lane order) and m
-    const Args a = {K, D, ldx, T, pivot_dev, img_dev, c_dev, nu_dev, lne, l.npad, st};
-    int rc;
-    if (D > 128) {
-        rc = x_dtype == HMMPRED_F32 ? launch_emission_plain((const float*)x_dev, a) : launch_emission_plain((const double*)x_dev, a);
-    } else {
-        const bool vec = D % 16 == 0 && (uintptr_t)x_dev % (4 * esz) == 0 && ldx % 4 == 0;
-        rc = x_dtype == HMMPRED_F32 ? launch_emission((const float*)x_dev, vec, a) : launch_emission((const double*)x_dev, vec, a);
-    }
+    int rc = emit_rows(K, D, x_dtype, x_dev, ldx, T, pivot_dev, img_dev, c_dev, nu_dev, lne, l.npad, rho, m, st);
     if (rc != HMMPRED_OK) return rc;
-    const unsigned pgrid = (unsigned)((T + gmmvb::kPrepSteps - 1) / gmmvb::kPrepSteps);
-    if (K <= 64)
-        hipLaunchKernelGGL(gmmvb::hmm_prep_kernel, dim3(pgrid), dim3(256),
-                           ((size_t)Kp * (gmmvb::kPrepSteps + 1) + gmmvb::kPrepSteps) * sizeof(double), st, (const double*)lne, l.npad,
-                           T, K, Kp, rho, m);
-    else
-        hipLaunchKernelGGL(gmmvb::hmm_prep_generic_kernel, dim3(pgrid), dim3(256), 0, st, (const double*)lne, l.npad, T, K, Kp, rho,
-                           m);
-    if ((rc = g_err.launched("hmmpred prep launch")) != HMMPRED_OK) return rc;
 
     // 2. the filter
     hipLaunchKernelGGL(first_step_kernel, dim3(1), dim3(kWalkThreads), 0, st, (const double*)rho, w0_dev, K, Kp, phi, s, starts, gate,

@@ -191,6 +191,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self._device, self._comm, self._verbose = device, SingleProcess(), verbose
         self._data_pass_factory = None          # test seam only (see gaussianmixture.LearnModel)
         self._hmmpred_pass_factory = None       # test seam only: (K, D) -> a stand-in for _hmmpred.HmmFilterPass
+        self._hmmbatch_pass = None              # the _hmmbatch.HmmBatchPass of the last calc_pred_logpdf(x, lengths=...)
         self._engine = self._x_dev = self._r_cache = None
         K, D = self.c_num_classes, self.c_degree
         (self.h0_eta_vec, self.h0_zeta_vecs, self.h0_m_vecs, self.h0_kappas, self.h0_nus, self.h0_w_mats) = _defaults(K, D)
@@ -521,7 +522,8 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self.p_lambda_mats[:] = (self.hn_kappas * self.p_nus / (self.hn_kappas + 1))[:, np.newaxis, np.newaxis] * self.hn_w_mats
         return self
 
-    def calc_pred_logpdf(self, x, *, start="last", assign=False, return_state=False, chunk_bytes=None):
+    def calc_pred_logpdf(self, x, *, lengths=None, start="last", assign=False, return_state=False, totals=False,
+                         chunk_bytes=None):
         """``ln p(x_t | x_0 .. x_{t-1}, data)`` of the rows of the sequence ``x`` under the predictive HMM - transitions
         ``p_a_mat``, Student-t emissions ``St(mu_k = p_mu_vecs, Lambda_k = p_lambda_mats, nu_k = p_nus)`` - float64 ``[T]``,
         in one device pass (``_hmmpred.HmmFilterPass``, DESIGN.md "Predictive log-density of a sequence").  The sum is the
@@ -541,11 +543,27 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         1 GiB) bounds the scratch: a longer sequence goes through in time slices, each started from the true ``phi A`` of
         the slice before; the input is not copied.  ``calc_pred_dist()`` runs first; nothing of the fit changes - ``hn_*``,
         ``gamma_vecs``, the statistics and an open fit engine stay as they were, and no fit workspace is created.  Up to 64
-        states the recursion runs chunk-parallel, up to 256 as one serial walk; more raise ``EngineLimitError``."""
-        from .. import _hmmpred, _stmix
+        states the recursion runs chunk-parallel, up to 256 as one serial walk; more raise ``EngineLimitError``.
+
+        ``lengths`` (1-D non-negative integers summing to the number of rows, else ``DataFormatError``) makes ``x`` the
+        concatenation of S independent sequences - windows, utterances, sessions - scored in one device pass
+        (``_hmmbatch.HmmBatchPass``, DESIGN.md "Predictive log-density of many sequences").  Each starts from ``start``:
+        the forms above apply to every sequence, an ``[S, K]`` matrix gives each its own row, checked like the vector.
+        ``z`` is then each sequence's own path, ``return_state`` gives ``[S, K]`` - an empty sequence's row is its start
+        vector - and ``totals=True`` (needs ``lengths``, else ``ParameterFormatError``) adds the sum of ``lnp`` over each
+        sequence, float64 ``[S]``, 0.0 for an empty one, summed in a fixed order.  The return is ``(lnp, z, state,
+        totals)`` without the parts not asked for.  Sequences of 4096 rows and more (up to 64 states) are filtered one by
+        one as a single sequence is, with the batch's pivot; ``chunk_bytes`` cuts the batch at sequence boundaries."""
+        from .. import _hmmbatch, _hmmpred, _stmix
         as_numpy = not isinstance(x, torch.Tensor)
         x = self._check_rows(x)
-        _hmmpred.start_vector(self, start)          # (refused before anything changes)
+        if lengths is None:
+            if totals:
+                raise ParameterFormatError("totals=True needs lengths: the sums are taken over the sequences it names")
+            _hmmpred.start_vector(self, start)          # (refused before anything changes)
+        else:
+            off = _hmmbatch.sequence_offsets(lengths, int(x.shape[0]))
+            _hmmbatch.start_vectors(self, start, len(off) - 1)
         self.calc_pred_dist()
 
         def params(dev):
@@ -555,6 +573,9 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
             u = torch.sqrt(t(scale))[:, None, None] * _stmix.precision_factor(t(self.hn_w_mats_inv))
             return t(self.p_a_mat), t(self.p_mu_vecs), t(self.p_nus), u
 
+        if lengths is not None:
+            return _hmmbatch.model_logpdf(self, x, as_numpy, off, start, bool(assign), bool(return_state), bool(totals),
+                                          chunk_bytes, params)
         return _hmmpred.model_logpdf(self, x, as_numpy, start, bool(assign), bool(return_state), chunk_bytes, params)
 
     def make_prediction(self, loss="squared"):
