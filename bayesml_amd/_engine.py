@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,6 +71,7 @@ SYMBOLS = {
     "hmmvb_out_len": (_i64, [_int]),
     "hmmvb_enable": (_int, [_vp]),
     "hmmvb_forward_backward": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "hmmvb_forward_backward_segments": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hmmvb_debug_readout": (_int, [_vp, _int, _i64, _i64, _vp, _vp]),
     "hmmvb_readout": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp]),
     "hmmvb_emission_target": (_int, [_vp, _int, _vp]),
@@ -593,6 +595,38 @@ class DataPass:
             _check(self.lib, self.lib.hmmvb_forward_backward(self._ws, self.rows, pi.data_ptr(), a.data_ptr(),
                                                              out.data_ptr(), self._stream()), "hmmvb_forward_backward")
         self._keep = self._keep[-3:] + [pi, a]
+        self._seg_first = None
+        return out[:K * K].view(K, K), out[K * K:K * K + K], out[K * K + K:K * K + 2 * K], out[K * K + 2 * K]
+
+    def segment_tables(self, off: np.ndarray):
+        """(off, order) on the device for ``forward_backward_segments``: the S + 1 row offsets (host int64) and the order in
+        which the waves take the sequences - lengths descending, stable, as ``_hmmbatch`` does it.  Made once per batch."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        order = np.argsort(-np.diff(off), kind="stable").astype(np.int32)
+        return torch.from_numpy(off).to(self.device), torch.from_numpy(order).to(self.device)
+
+    def forward_backward_segments(self, pi_tilde, a_tilde, off: torch.Tensor, order: torch.Tensor, out: torch.Tensor = None):
+        """``forward_backward`` over the S sequences with device row offsets ``off`` [S + 1] (int64) in the walking order
+        ``order`` [S] (int32), see ``segment_tables``: (ms, sum of the first rows' gamma, sum of the last rows' gamma,
+        sum ln c), nothing counted or carried across a boundary (hmmvb_forward_backward_segments; up to 64 states)."""
+        K = self.K
+        pi = _f64(pi_tilde, (K,), self.device)
+        a = _f64(a_tilde, (K, K), self.device)
+        S = order.numel()
+        if (off.dtype != torch.int64 or order.dtype != torch.int32 or off.numel() != S + 1 or off.device != self.device
+                or order.device != self.device or not off.is_contiguous() or not order.is_contiguous()):
+            raise ValueError("off must be S + 1 int64 row offsets and order S int32 sequence indices on the engine's device")
+        n_out = int(self.lib.hmmvb_out_len(K))
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != n_out or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float64 tensor of hmmvb_out_len(K) elements on the engine's device")
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hmmvb_forward_backward_segments(
+                self._ws, self.rows, S, off.data_ptr(), order.data_ptr(), pi.data_ptr(), a.data_ptr(), out.data_ptr(),
+                self._stream()), "hmmvb_forward_backward_segments")
+        self._keep = self._keep[-3:] + [pi, a, off, order]
+        self._seg_first = off[:-1]               # (the xi read-out is 0 there: hmm_readout)
         return out[:K * K].view(K, K), out[K * K:K * K + K], out[K * K + K:K * K + 2 * K], out[K * K + 2 * K]
 
     def viterbi(self, ln_pi_tilde, ln_a_tilde) -> torch.Tensor:
@@ -619,6 +653,9 @@ class DataPass:
                                                     out.data_ptr(), self._stream()), "hmmvb_readout")
         if a is not None:
             torch.cuda.current_stream(self.device).synchronize()          # a must outlive the kernel
+            first = getattr(self, "_seg_first", None)
+            if first is not None:             # after a pass over many sequences: xi = 0 at every sequence's first row
+                out[first[(first >= row0) & (first < row0 + n)] - row0] = 0.0
         return out
 
     def hmm_debug(self, what, row0=0, n=None):

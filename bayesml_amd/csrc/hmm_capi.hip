@@ -11,6 +11,7 @@
 #include "launch.h"
 #include "hmm_generic.h"
 #include "hmm_wide.h"
+#include "hmmseg_kernels.h"
 
 #include <cstdlib>
 
@@ -103,6 +104,7 @@ struct gmmvb_hmm_state {
     bool gate_two_stage = false;  // the pass whose gates are pending had a short first stage
     int spec_hold = 0, spec_hold_len = 8, last_gate = -1;   // last_gate: -1 no forgetting pass, 0 it stood, 1 products path behind it
     bool fuse_emission = false;   // hmmvb_emission_target: gmmvb_estep writes rho' / mx here (hmm.h H0 + H1) and no ln rho array
+    int64_t seg_waves = 0;        // developer switch GMMVB_HMMSEG_WAVES: at most so many xi slabs in run_segments (0: xi_slab_cap)
 };
 
 namespace {
@@ -401,6 +403,59 @@ hipError_t run(gmmvb_workspace* ws, gmmvb_hmm_state* h, int64_t T, const double*
     // waves of the last block beyond n_waves write slabs too (zeros): include them only if they exist
     const int64_t n_slabs = xi_fused ? (int64_t)grid * 4 : (n_waves > 0 ? ((n_waves + 3) / 4) * 4 : 0);
     return finish_pass(h, st, T, a_tilde, n_slabs, /*w_valid=*/!xi_fused, out);
+}
+
+// ---- up to 64 states, many sequences laid end to end (hmmseg_kernels.h) ----------------------------------------------------
+// Every sequence start is an exact boundary, so the pass is a fixed launch sequence: no chunks, no sweeps, no gate, nothing
+// the host decides from device results.  The rows are the same rows: rho', alpha, gamma, w, c' and the xi slabs are the
+// single-sequence pass's buffers, and the g0 / gl partial sums take the head of the (unused) chunk products.
+template <int KT>
+hipError_t run_segments(gmmvb_workspace* ws, gmmvb_hmm_state* h, int64_t T, int64_t n_seq, const int64_t* off, const int32_t* order,
+                        const double* pi_tilde, const double* a_tilde, double* out, hipStream_t st) {
+    const int K = h->K, Kp = h->Kp;
+    if (ws->e_state != 4)          // (4: the emission kernel has written rho' and mx itself)
+        hipLaunchKernelGGL(hmm_prep_kernel, dim3((unsigned)((T + kPrepSteps - 1) / kPrepSteps)), dim3(256),
+                           ((size_t)Kp * (kPrepSteps + 1) + kPrepSteps) * sizeof(double), st, ws->lnrho, ws->npad, T, K, Kp, h->rho_tm,
+                           h->mx);
+    const int64_t n_sheaves = (n_seq + kSegSheaf - 1) / kSegSheaf;
+    const int64_t wgs = (n_sheaves + kSegWaves - 1) / kSegWaves;
+    hipLaunchKernelGGL((hmmseg_forward_kernel<KT>), dim3((unsigned)wgs), dim3(64 * kSegWaves), 0, st, h->rho_tm, pi_tilde, a_tilde, K,
+                       off, order, n_seq, h->alpha_tm, h->cprime);
+    // the xi sum inside the backward kernel, a slab per wave (up to 32 states, as in run<KT>): its waves take several sheaves
+    // each where there are more sheaves than slabs
+    const bool xi_fused = KT <= 2 && h->xi_slab_cap >= kSegWaves && !h->xi_separate;
+    int64_t n_slabs = 0;
+    if constexpr (KT <= 2) {
+        if (xi_fused) {
+            const int64_t slabs = h->seg_waves > 0 ? std::min(h->seg_waves, h->xi_slab_cap) : h->xi_slab_cap;
+            const int64_t grid = std::min<int64_t>(wgs, slabs / kSegWaves);
+            hipLaunchKernelGGL((hmmseg_backward_kernel<KT, true>), dim3((unsigned)grid), dim3(64 * kSegWaves), 0, st, h->rho_tm, a_tilde,
+                               K, off, order, n_seq, h->alpha_tm, h->cprime, h->gamma_tm, h->w_tm, h->xi_slabs);
+            n_slabs = grid * kSegWaves;
+        }
+    }
+    if (!xi_fused) {
+        // w = 0 at every first row keeps alpha_{last of s-1} (x) w_{first of s} out of the sum over all rows
+        hipLaunchKernelGGL((hmmseg_backward_kernel<KT, false>), dim3((unsigned)wgs), dim3(64 * kSegWaves), 0, st, h->rho_tm, a_tilde, K,
+                           off, order, n_seq, h->alpha_tm, h->cprime, h->gamma_tm, h->w_tm, nullptr);
+        if (T > 1) {
+            const int64_t steps = round_up((T - 1 + h->xi_waves - 1) / h->xi_waves, 4);
+            const int64_t n_waves = (T - 1 + steps - 1) / steps;
+            hipLaunchKernelGGL((hmm_xi_sum_kernel<KT>), dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, h->alpha_tm, h->w_tm, T,
+                               steps, h->xi_slabs);
+            n_slabs = ((n_waves + 3) / 4) * 4;
+        }
+    }
+    h->last_gate = -1;
+    if (hipError_t e = finish_pass(h, st, T, a_tilde, n_slabs, /*w_valid=*/!xi_fused, out); e != hipSuccess) return e;
+    // g0 / gl over the sequences' ends, written over the two slots finish_pass filled from rows 0 and T - 1
+    const int64_t room = h->max_chunks * Kp / 2;                    // [2][K] partial sums each, in h->prod
+    const int64_t n_part = std::max<int64_t>(1, std::min<int64_t>({256, (n_seq + kSegEndsSeqs - 1) / kSegEndsSeqs, room}));
+    const int64_t per = (n_seq + n_part - 1) / n_part;
+    hipLaunchKernelGGL(hmmseg_ends_partial_kernel, dim3((unsigned)n_part), dim3(256), 0, st, h->gamma_tm, K, Kp, off, n_seq, per,
+                       h->prod);
+    hipLaunchKernelGGL(hmmseg_ends_kernel, dim3(1), dim3(128), 0, st, h->prod, n_part, K, out);
+    return hipGetLastError();
 }
 
 // the kernels of hmm_generic.h and hmm_wide.h ask for more than 48 KB of dynamic LDS at some state counts
@@ -747,6 +802,7 @@ int hmmvb_enable(gmmvb_workspace* ws) {
     // wave; shorter ones at most ~850 chunks (narrow_chunk_len)
     h->xi_slab_cap = std::max<int64_t>(h->xi_waves + 4, h->generic ? 0 : h->npad / (16 * (kHmmLongChunk / 2)) + 72);
     h->xi_separate = dev_env("GMMVB_HMM_XI_SEPARATE") != nullptr;
+    if (const char* v = dev_env("GMMVB_HMMSEG_WAVES")) h->seg_waves = std::max<int64_t>(kSegWaves, std::atoll(v));
     // chunk boundary vectors: more than 128 states walk chunks of kHmmGenericChunk steps in the forgetting pass (run_generic)
     h->vec_chunks = (h->generic && !h->wide) ? h->npad / kHmmGenericChunk + 2 : h->max_chunks;
     for (const HmmBuf& b : hmm_buffers(h)) {
@@ -864,6 +920,29 @@ int hmmvb_forward_backward(gmmvb_workspace* ws, int64_t n_rows, const double* pi
         });
     }
     if (e != hipSuccess) return fail(GMMVB_EHIP, what, e);
+    ws->e_state = 3;
+    return GMMVB_OK;
+}
+
+int hmmvb_forward_backward_segments(gmmvb_workspace* ws, int64_t n_rows, int64_t n_seq, const int64_t* off_dev,
+                                    const int32_t* order_dev, const double* pi_tilde_dev, const double* a_tilde_dev,
+                                    double* out_dev, void* stream) {
+    if (!ws || !off_dev || !order_dev || !pi_tilde_dev || !a_tilde_dev || !out_dev) return fail(GMMVB_EINVAL, "null argument");
+    if (n_seq < 1 || n_rows < 1) return fail(GMMVB_EINVAL, "hmmvb_forward_backward_segments: at least one sequence and one row");
+    if (!ws->hmm) return fail(GMMVB_ESTATE, "hmmvb_enable has not been called");
+    gmmvb_hmm_state* h = ws->hmm;
+    if (h->generic || h->KT < 1 || h->KT > 4)
+        return fail(GMMVB_EUNSUPPORTED, "hmmvb_forward_backward_segments: at most 64 states");
+    if ((ws->e_state != 1 && ws->e_state != 4) || ws->e_rows != n_rows)
+        return fail(GMMVB_ESTATE, "no emission ln rho for these rows: call gmmvb_estep first");
+    // (the outcome of an earlier forgetting pass steers nothing here, and this pass has none: hmmvb_last_boundary_pass is -1)
+    consume_gate(h, /*wait=*/false);
+    h->gate_pending = false;
+    const hipError_t e = dispatch_kt<1, 4>(h->KT, [&](auto kt) {
+        return run_segments<decltype(kt)::value>(ws, h, n_rows, n_seq, off_dev, order_dev, pi_tilde_dev, a_tilde_dev, out_dev,
+                                                 (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return fail(GMMVB_EHIP, "HMM forward-backward launch (segments)", e);
     ws->e_state = 3;
     return GMMVB_OK;
 }

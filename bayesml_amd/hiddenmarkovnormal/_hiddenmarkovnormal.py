@@ -288,11 +288,15 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self._refresh_host_features(q)
 
     # ------------------------------------------------------------------ the data pass
-    def _pass(self, eng, xd, q, s_prev):
-        """_update_q_z (ref:1020-1026) on the GPU: emission -> forward-backward -> statistics."""
+    def _pass(self, eng, xd, q, s_prev, seg=None):
+        """_update_q_z (ref:1020-1026) on the GPU: emission -> forward-backward -> statistics.  ``seg``: the (host offsets,
+        device offsets, device order) of a fit from many sequences, each forward-backward on its own."""
         eng.set_params(q.c, q.m, q.u)
         eng.estep(xd)
-        ms, g0, gl, sum_ln_c = eng.forward_backward(q.pi_tilde, q.a_tilde)
+        if seg is None:
+            ms, g0, gl, sum_ln_c = eng.forward_backward(q.pi_tilde, q.a_tilde)
+        else:
+            ms, g0, gl, sum_ln_c = eng.forward_backward_segments(q.pi_tilde, q.a_tilde, seg[1], seg[2])
         ns, h, a, B = eng.split_stats(eng.mstep(xd))
         x_bar, s = _kside.moments_from_stats(ns, a, B, eng.pivot, s_prev)
         # sum gamma ln rho (ref:905) from the moments, in the closed form the reference uses for E[ln p(x|z)] (ref:871-877):
@@ -307,16 +311,33 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         return bool(xd.is_cuda and self._data_pass_factory is None and xd.shape[0] < 4096 and self.c_num_classes <= 64)
 
     @staticmethod
-    def _stepper_pass(eng, xd, ks):
+    def _stepper_pass(eng, xd, ks, seg=None):
         """_update_q_z (ref:1020-1026) under the stepper's current posterior: emission -> forward-backward -> statistics,
         written into the stepper's buffers (the K-sized rest of the iteration is ``ks.step()``)."""
         q = ks.q
         eng.set_params(q.c, q.m, q.u)
         eng.estep(xd)
-        eng.forward_backward(q.pi_tilde, q.a_tilde, out=ks.fb)
+        if seg is None:
+            eng.forward_backward(q.pi_tilde, q.a_tilde, out=ks.fb)
+        else:
+            eng.forward_backward_segments(q.pi_tilde, q.a_tilde, seg[1], seg[2], out=ks.fb)
         eng.mstep(xd, out=ks.stats)
 
-    def _random_pass(self, eng, xd, ks):
+    @staticmethod
+    def _random_segments(xi, off):
+        """The random-responsibility start of S sequences from the pooled draw xi [T, K, K] (changed in place):
+        (gamma, ms, g0, gl).  xi is 0 at every first row; the first row of a sequence with a second row takes
+        gamma = xi_next.sum(axis=1), the reference's rule (ref:946), a sequence of one row its own marginal (taken before
+        the row is zeroed); ms = sum xi; g0 / gl = the sums of gamma over the sequences' first / last rows."""
+        lens = np.diff(off)
+        first, n = off[:-1][lens > 0], lens[lens > 0]
+        own = xi[first].sum(axis=1)
+        xi[first] = 0.0
+        gamma = xi.sum(axis=1)
+        gamma[first] = np.where((n > 1)[:, np.newaxis], xi[np.minimum(first + 1, len(xi) - 1)].sum(axis=2), own)
+        return gamma, xi.sum(axis=0), gamma[first].sum(axis=0), gamma[first + n - 1].sum(axis=0)
+
+    def _random_pass(self, eng, xd, ks, seg=None):
         """_init_random_responsibility (ref:941-950): gamma and ms from host Dirichlet draws, written where the data pass
         writes them (the stepper's statistics block and forward-backward summary); ln rho = 0 and cs = 1 keep their
         _init_fb_params values (ref:931-939), so both N-sized sums of the lower bound are 0."""
@@ -326,20 +347,51 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
             ms = np.zeros([K, K])
         else:
             xi = self.rng.dirichlet(np.ones(K ** 2), T).reshape(T, K, K)
-            xi[0] = 0.0
-            gamma = xi.sum(axis=1)
-            gamma[0] = xi[1].sum(axis=1)
-            ms = xi.sum(axis=0)
+            if seg is not None:
+                gamma, ms, g0, gl = self._random_segments(xi, seg[0])
+            else:
+                xi[0] = 0.0
+                gamma = xi.sum(axis=1)
+                gamma[0] = xi[1].sum(axis=1)
+                ms = xi.sum(axis=0)
+        if seg is None:
+            g0, gl = gamma[0], gamma[-1]
         eng.load_responsibilities(torch.from_numpy(np.ascontiguousarray(gamma)).to(dev))
         eng.mstep(xd, out=ks.stats)
-        ks.fb.copy_(torch.from_numpy(np.concatenate([ms.reshape(-1), gamma[0], gamma[-1], [0.0]])).to(dev))
+        ks.fb.copy_(torch.from_numpy(np.concatenate([ms.reshape(-1), g0, gl, [0.0]])).to(dev))
 
     def _vl(self, prior, q, st):
         return _kside.hmm_lower_bound(prior, q, st["ns"], st["ms"], st["x_bar"], st["s"], st["g0"],
                                       st["sum_g_ln_rho"], st["sum_ln_c"])
 
-    def update_posterior(self, x, max_itr=100, num_init=10, tolerance=1.0E-8, init_type="subsampling"):
-        """Variational-Bayes update of ``hn_*`` from one observed sequence (driver of ref:1028-1134)."""
+    def _segment_offsets(self, x, lengths):
+        """The host row offsets of ``update_posterior(x, lengths=...)``, or None where the call is today's single-sequence
+        one: no ``lengths``, or exactly one non-empty sequence."""
+        if lengths is None:
+            return None
+        from .._hmmbatch import sequence_offsets
+        off = sequence_offsets(lengths, int(self._check_rows(x).shape[0]))
+        if np.count_nonzero(np.diff(off)) <= 1:
+            return None
+        if self.c_num_classes > self.SEGMENT_STATES:
+            raise ParameterFormatError(f"update_posterior(x, lengths=...) fits more than one sequence with at most "
+                                       f"{self.SEGMENT_STATES} states: c_num_classes={self.c_num_classes}")
+        return off
+
+    SEGMENT_STATES = 64        # the segment kernels cover the narrow forward-backward engine's range (csrc/hmmseg_kernels.h)
+
+    def update_posterior(self, x, max_itr=100, num_init=10, tolerance=1.0E-8, init_type="subsampling", *, lengths=None):
+        """Variational-Bayes update of ``hn_*`` from one observed sequence (driver of ref:1028-1134).
+
+        ``lengths`` (extension): a 1-dimensional array of non-negative integers that sum to the number of rows of ``x`` -
+        the rows are then S independent sequences laid end to end (empty ones contribute nothing), fitted together in one
+        device pass per iteration: every sequence starts from pi, no transition is counted and no alpha carried across a
+        boundary (ms = the sum of xi over the rows that are not a sequence's first, the lower bound's gamma_0 terms read
+        the sum of the first rows' gamma).  Without ``lengths``, or with one non-empty sequence, the call is the
+        single-sequence one, bit for bit.  More than one sequence needs c_num_classes <= 64 (``ParameterFormatError``
+        beyond).  A member of any length is correct, but costs its own length in serial steps: a very long member is not
+        routed to the chunk-parallel path."""
+        off = self._segment_offsets(x, lengths)
         eng, xd = self._open(x)
         eng.enable_hmm()
         eng.hmm_skip_h(True)
@@ -355,10 +407,12 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         # _kside.HmmKStepper); the data pass writes its statistics and the forward-backward summary into the stepper's buffers
         ks = _kside.HmmKStepper(prior, eng.pivot, eng.stats_len)
         ks.s_prev.copy_(s_prev)
-        whole_iteration = self._whole_iteration_graph(xd)
+        # many sequences: offsets and walking order uploaded once; the data pass runs outside the captured graph
+        seg = None if off is None else (off,) + eng.segment_tables(off)
+        whole_iteration = seg is None and self._whole_iteration_graph(xd)
 
         def data_pass():
-            self._stepper_pass(eng, xd, ks)
+            self._stepper_pass(eng, xd, ks, seg)
 
         for i in range(num_init):
             self.reset_hn_params()
@@ -372,7 +426,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
             elif init_type == "random_responsibility":
                 ks.load(q)
                 ks.h_scale.fill_(0.0)          # (no emission in this pass: both N-sized sums of the lower bound are 0, ref:931-939)
-                self._random_pass(eng, xd, ks)
+                self._random_pass(eng, xd, ks, seg)
             else:
                 raise ValueError(f"init_type={init_type} is unsupported. This function supports only "
                                  '"subsampling" and "random_responsibility"')
@@ -414,7 +468,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         if terms is not None:
             for k, v in terms.items():
                 setattr(self, "vl" if k == "vl" else "_vl_" + k, float(v))
-        st = self._pass(eng, xd, q, s_prev)                      # ref:1133
+        st = self._pass(eng, xd, q, s_prev, seg)                 # ref:1133
         self._store_stats(st)
         return self
 

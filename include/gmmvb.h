@@ -216,6 +216,18 @@ int64_t hmmvb_out_len(int K);
 int hmmvb_enable(gmmvb_workspace* ws);
 int hmmvb_forward_backward(gmmvb_workspace* ws, int64_t n_rows, const double* pi_tilde_dev, const double* a_tilde_dev,
                            double* out_dev, void* stream);
+/* The same pass over n_seq independent sequences laid end to end (up to 64 states; additive in ABI version 8): sequence s is
+ * the rows off[s] .. off[s + 1] - 1 (off_dev [n_seq + 1], off[0] = 0, off[n_seq] = n_rows; empty sequences contribute
+ * nothing), order_dev [n_seq] is a permutation of the sequences - the waves take 16 consecutive entries each, so lengths
+ * descending keep a wave's members alike; the result does not depend on it.  Every sequence starts from pi_tilde and ends
+ * with beta = 1, no xi is counted across a boundary, and
+ *   out = [ ms = sum_s sum_{t > first(s)} xi_t | sum_s gamma_first(s) | sum_s gamma_last(s) | sum_t ln c_t ].
+ * It leaves what hmmvb_forward_backward leaves (gamma as the responsibilities, the alpha / beta read-outs; the xi read-out
+ * at a sequence's first row is the junction term and is the caller's to mask).  Enqueues only; takes no host-side decision;
+ * hmmvb_last_boundary_pass reports -1 after it.  More than 64 states: GMMVB_EUNSUPPORTED. */
+int hmmvb_forward_backward_segments(gmmvb_workspace* ws, int64_t n_rows, int64_t n_seq, const int64_t* off_dev,
+                                    const int32_t* order_dev, const double* pi_tilde_dev, const double* a_tilde_dev,
+                                    double* out_dev, void* stream);
 /* How the last hmmvb_forward_backward call got its chunk boundary vectors (diagnostics / tests; waits for that call):
  *   -1  from the chunk transfer products (short sequences, or the forgetting pass held off),
  *    0  from the forgetting pass - both recursions swept from uniform start vectors, the replays' own boundary vectors agreed
