@@ -44,21 +44,25 @@ def segment_oracle(x, q, off):
                 lnc=float((np.log(cs) + mx[:, 0]).sum()))
 
 
-def segment_pass(x, q, off, order=None, fused=False, pivot=None):
-    """One data pass over the segments through the C ABI, as device_pass of tests/test_gpu_hmm.py runs the single sequence."""
+def segment_pass(x, q, off, order=None, fused=False, pivot=None, eng=None, keep=False):
+    """One data pass over the segments through the C ABI, as device_pass of tests/test_gpu_hmm.py runs the single sequence.
+    ``eng``: an engine an earlier call left open with ``keep`` (built for at least as many rows); the result then carries it as
+    ``eng``.  ``ln_rho`` is the array the engine holds after ``estep`` (None with the fused emission, which forms none)."""
     from bayesml_amd import _kside
     from bayesml_amd._engine import DataPass
     dev, (K, D) = torch.device("cuda", 0), q.m.shape
     t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)   # noqa: E731
     f = _kside.features(_kside.PostT(torch.ones(K, dtype=torch.float64, device=dev), t(q.m), t(q.kappa), t(q.nu), t(q.w_inv)))
     xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    eng = DataPass(K, D, xd.dtype, x.shape[0], dev)
+    if eng is None:
+        eng = DataPass(K, D, xd.dtype, x.shape[0], dev)
     eng.set_pivot(xd[:4096].to(torch.float64).mean(dim=0) if pivot is None else t(pivot))
     eng.prepare_rows(xd)
     eng.set_params((f.e_ln_lambda_det - D * _kside.LN_2PI - D / f.kappa) / 2.0, f.m, f.u)
     eng.enable_hmm()
     assert eng.emission_target(fused) == fused
     eng.estep(xd)
+    ln_rho = None if fused else eng.ln_rho().cpu().numpy()
     off_dev, order_dev = eng.segment_tables(off)
     if order is not None:
         order_dev = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
@@ -66,8 +70,9 @@ def segment_pass(x, q, off, order=None, fused=False, pivot=None):
     out = dict(ms=ms.cpu().numpy(), g0=g0.cpu().numpy(), gl=gl.cpu().numpy(), lnc=float(lnc),
                ns=eng.split_stats(eng.mstep(xd))[0].cpu().numpy(), gamma=eng.responsibilities().cpu().numpy(), alpha=eng.hmm_debug(0).cpu().numpy(),
                cprime=eng.hmm_debug(1).cpu().numpy(), xi=eng.hmm_readout("xi", 0, None, t(q.a_tilde)).cpu().numpy(),
-               gate=eng.last_boundary_pass())
-    eng.close()
+               gate=eng.last_boundary_pass(), ln_rho=ln_rho, eng=eng if keep else None)
+    if not keep:
+        eng.close()
     return out
 
 
