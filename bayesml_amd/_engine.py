@@ -79,6 +79,7 @@ SYMBOLS = {
     "hmmvb_last_boundary_pass": (_int, [_vp]),
     "hmmvb_last_viterbi_pass": (_int, [_vp]),
     "hmmvb_viterbi": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "hmmvb_viterbi_segments": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gmmvb_profile_enable": (_int, [_vp, _int]),
     "gmmvb_profile_last_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "gmmvb_profile_spans": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_int)]),
@@ -639,6 +640,25 @@ class DataPass:
             _check(self.lib, self.lib.hmmvb_viterbi(self._ws, self.rows, pi.data_ptr(), a.data_ptr(), z.data_ptr(),
                                                     self._stream()), "hmmvb_viterbi")
         torch.cuda.current_stream(self.device).synchronize()     # pi / a must outlive the kernels
+        return z
+
+    def viterbi_segments(self, ln_pi_tilde, ln_a_tilde, off: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+        """``viterbi`` over the S sequences with device row offsets ``off`` [S + 1] (int64) in the walking order ``order`` [S]
+        (int32), see ``segment_tables``: every sequence's own most probable path, each started from ln pi~ (int32 [rows];
+        hmmvb_viterbi_segments; up to 64 states)."""
+        K = self.K
+        pi = _f64(ln_pi_tilde, (K,), self.device)
+        a = _f64(ln_a_tilde, (K, K), self.device)
+        S = order.numel()
+        if (off.dtype != torch.int64 or order.dtype != torch.int32 or off.numel() != S + 1 or off.device != self.device
+                or order.device != self.device or not off.is_contiguous() or not order.is_contiguous()):
+            raise ValueError("off must be S + 1 int64 row offsets and order S int32 sequence indices on the engine's device")
+        z = torch.empty(self.rows, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hmmvb_viterbi_segments(
+                self._ws, self.rows, S, off.data_ptr(), order.data_ptr(), pi.data_ptr(), a.data_ptr(), z.data_ptr(),
+                self._stream()), "hmmvb_viterbi_segments")
+        torch.cuda.current_stream(self.device).synchronize()     # pi / a must outlive the kernel
         return z
 
     def hmm_readout(self, what: str, row0=0, n=None, a_tilde=None) -> torch.Tensor:

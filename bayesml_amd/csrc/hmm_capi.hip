@@ -12,6 +12,7 @@
 #include "hmm_generic.h"
 #include "hmm_wide.h"
 #include "hmmseg_kernels.h"
+#include "hmmvit_kernels.h"
 
 #include <cstdlib>
 
@@ -772,6 +773,39 @@ int viterbi_wave_kt(const VitArgs& v) {
 }
 int viterbi_wave(const VitArgs& v) { return dispatch_kt<1, 4>(v.h->KT, [&](auto kt) { return viterbi_wave_kt<decltype(kt)::value>(v); }); }
 
+// What every Viterbi entry point does to the state before it launches: the pass owns the forward-backward pass's buffers
+// (chunk products, boundary vectors, xi slabs, w_tm) as scratch, so whatever that pass left is gone - said explicitly, not
+// only through e_state (hmmvb_readout checks gamma_rows) - and no coalescence pass has run yet.
+void viterbi_takes_buffers(gmmvb_hmm_state* h) {
+    h->vit_coalesced = false;
+    h->w_valid = false;
+    h->gamma_rows = 0;
+    h->gamma_cm_valid = false;
+}
+
+// ---- Viterbi over many sequences, up to 64 states (hmmvit_kernels.h): forward walk and backtrack in one launch -------------
+struct VitSegArgs {
+    const VitArgs& v; int64_t n_seq; const int64_t* off; const int32_t* order;
+};
+template <int Kq>
+int viterbi_segments_kq(const VitSegArgs& s) {
+    const VitArgs& v = s.v;
+    constexpr int64_t per_wg = (int64_t)kVitSegWaves * (64 / Kq);      // sequences of a workgroup
+    const int64_t wgs = (s.n_seq + per_wg - 1) / per_wg;
+    if (wgs > 0x7fffffff) return fail(GMMVB_EUNSUPPORTED, "hmmvb_viterbi_segments: too many sequences for one grid");
+    hipLaunchKernelGGL((hmmvit_segments_kernel<Kq>), dim3((unsigned)wgs), dim3(64 * kVitSegWaves), 0, v.st, v.ws->lnrho, v.ws->npad,
+                       v.ln_pi_tilde, v.ln_a_tilde, v.h->K, v.h->Kp, s.off, s.order, s.n_seq, v.h->phi, v.z);
+    return launched("viterbi launch (segments)");
+}
+int viterbi_segments(const VitSegArgs& s) {
+    const int K = s.v.h->K;
+    if (K <= 4) return viterbi_segments_kq<4>(s);
+    if (K <= 8) return viterbi_segments_kq<8>(s);
+    if (K <= 16) return viterbi_segments_kq<16>(s);
+    if (K <= 32) return viterbi_segments_kq<32>(s);
+    return viterbi_segments_kq<64>(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -852,16 +886,27 @@ int hmmvb_viterbi(gmmvb_workspace* ws, int64_t n_rows, const double* ln_pi_tilde
     if (ws->e_state != 1 || ws->e_rows != n_rows)
         return fail(GMMVB_ESTATE, "no emission ln rho for these rows: call gmmvb_estep first");
     gmmvb_hmm_state* h = ws->hmm;
-    h->vit_coalesced = false;
-    // the pass takes the forward-backward pass's buffers as scratch (chunk products, boundary vectors, xi slabs, w_tm): whatever
-    // that pass left is gone - said explicitly, not only through e_state (hmmvb_readout checks gamma_rows)
-    h->w_valid = false;
-    h->gamma_rows = 0;
-    h->gamma_cm_valid = false;
+    viterbi_takes_buffers(h);
     const VitArgs v{ws, h, n_rows, ln_pi_tilde_dev, ln_a_tilde_dev, z_dev, (hipStream_t)stream};
     if (h->wide && h->phi && n_rows >= kHmmWideMinSteps) return viterbi_wide(v);
     if (h->generic) return viterbi_generic(v);
     return n_rows >= kVitChunkedFrom ? viterbi_chunked(v) : viterbi_wave(v);
+}
+
+int hmmvb_viterbi_segments(gmmvb_workspace* ws, int64_t n_rows, int64_t n_seq, const int64_t* off_dev, const int32_t* order_dev,
+                           const double* ln_pi_tilde_dev, const double* ln_a_tilde_dev, int32_t* z_dev, void* stream) {
+    if (!ws || !off_dev || !order_dev || !ln_pi_tilde_dev || !ln_a_tilde_dev || !z_dev) return fail(GMMVB_EINVAL, "null argument");
+    if (n_seq < 1) return fail(GMMVB_EINVAL, "hmmvb_viterbi_segments: at least one sequence");
+    if (!ws->hmm) return fail(GMMVB_ESTATE, "hmmvb_enable has not been called");
+    gmmvb_hmm_state* h = ws->hmm;
+    if (h->generic || h->KT < 1 || h->KT > 4 || !h->phi) return fail(GMMVB_EUNSUPPORTED, "hmmvb_viterbi_segments: at most 64 states");
+    if (ws->e_state == 4)
+        return fail(GMMVB_ESTATE, "the last gmmvb_estep formed no ln rho array (hmmvb_emission_target 1): run it with target 0");
+    if (ws->e_state != 1 || ws->e_rows != n_rows)
+        return fail(GMMVB_ESTATE, "no emission ln rho for these rows: call gmmvb_estep first");
+    viterbi_takes_buffers(h);
+    const VitArgs v{ws, h, n_rows, ln_pi_tilde_dev, ln_a_tilde_dev, z_dev, (hipStream_t)stream};
+    return viterbi_segments(VitSegArgs{v, n_seq, off_dev, order_dev});
 }
 
 int hmmvb_last_viterbi_pass(gmmvb_workspace* ws) {

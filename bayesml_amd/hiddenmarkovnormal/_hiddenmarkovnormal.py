@@ -365,8 +365,8 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
                                       st["sum_g_ln_rho"], st["sum_ln_c"])
 
     def _segment_offsets(self, x, lengths):
-        """The host row offsets of ``update_posterior(x, lengths=...)``, or None where the call is today's single-sequence
-        one: no ``lengths``, or exactly one non-empty sequence."""
+        """The host row offsets of ``update_posterior`` / ``estimate_latent_vars(x, lengths=...)``, or None where the call is
+        the single-sequence one: no ``lengths``, or exactly one non-empty sequence."""
         if lengths is None:
             return None
         from .._hmmbatch import sequence_offsets
@@ -374,7 +374,7 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         if np.count_nonzero(np.diff(off)) <= 1:
             return None
         if self.c_num_classes > self.SEGMENT_STATES:
-            raise ParameterFormatError(f"update_posterior(x, lengths=...) fits more than one sequence with at most "
+            raise ParameterFormatError(f"lengths=... takes more than one sequence with at most "
                                        f"{self.SEGMENT_STATES} states: c_num_classes={self.c_num_classes}")
         return off
 
@@ -663,8 +663,22 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
                               init_type=init_type)
         return prediction
 
-    def estimate_latent_vars(self, x, loss="0-1", viterbi=True):
-        """One-hot Viterbi path (``viterbi=True``, "0-1" only) or posterior marginals (ref:1425-1499)."""
+    def estimate_latent_vars(self, x, loss="0-1", viterbi=True, *, lengths=None):
+        """One-hot Viterbi path (``viterbi=True``, "0-1" only) or posterior marginals (ref:1425-1499).
+
+        ``lengths`` (extension, as in ``update_posterior``): the rows are S independent sequences laid end to end, decoded
+        in one device pass.  ``viterbi=True``: every sequence's own most probable path, each started from pi - not the path
+        of the concatenation, which runs across the boundaries; ``viterbi=False``: every sequence's own marginals.  Without
+        ``lengths``, or with one non-empty sequence, the call is the single-sequence one, bit for bit.  More than one
+        sequence needs c_num_classes <= 64 (``ParameterFormatError`` beyond).  ``lengths`` and ``loss`` are checked before
+        the device is touched."""
+        off = self._segment_offsets(x, lengths)
+        if viterbi and loss != "0-1":
+            raise CriteriaError(f"loss=\"{loss}\" is unsupported. "
+                                "When viterbi == True, this function supports only \"0-1\".")
+        if not viterbi and loss not in ("squared", "0-1", "KL"):
+            raise CriteriaError(f"loss=\"{loss}\" is unsupported. "
+                                "When viterbi == False, This function supports \"squared\", \"0-1\", and \"KL\".")
         eng, xd = self._open(x)
         eng.enable_hmm()
         eng.hmm_skip_h(True)
@@ -672,22 +686,20 @@ class LearnModel(DeviceModel, base.Posterior, base.PredictiveMixin):
         self._length = xd.shape[0]
         q = self._post_tensors(xd.device)
         K = self.c_num_classes
+        seg = None if off is None else (off,) + eng.segment_tables(off)
         if viterbi:
-            if loss != "0-1":
-                raise CriteriaError(f"loss=\"{loss}\" is unsupported. "
-                                    "When viterbi == True, this function supports only \"0-1\".")
             eng.set_params(q.c, q.m, q.u)
             eng.estep(xd)
-            z = eng.viterbi(q.ln_pi_tilde, q.ln_a_tilde).to("cpu").numpy()
-            return np.eye(K, dtype=int)[z]
+            if seg is None:
+                z = eng.viterbi(q.ln_pi_tilde, q.ln_a_tilde)
+            else:
+                z = eng.viterbi_segments(q.ln_pi_tilde, q.ln_a_tilde, seg[1], seg[2])
+            return np.eye(K, dtype=int)[z.to("cpu").numpy()]
         s_prev = torch.as_tensor(self.s_mats, dtype=torch.float64, device=xd.device)
-        self._store_stats(self._pass(eng, xd, q, s_prev))
+        self._store_stats(self._pass(eng, xd, q, s_prev, seg))
         if loss in ("squared", "KL"):
             return self.gamma_vecs
-        if loss == "0-1":
-            return np.eye(K, dtype=int)[eng.argmax().to("cpu").numpy()]
-        raise CriteriaError(f"loss=\"{loss}\" is unsupported. "
-                            "When viterbi == False, This function supports \"squared\", \"0-1\", and \"KL\".")
+        return np.eye(K, dtype=int)[eng.argmax().to("cpu").numpy()]
 
     def estimate_latent_vars_and_update(self, x, loss="0-1", viterbi=True, max_itr=100, num_init=10,
                                         tolerance=1.0E-8, init_type="subsampling"):

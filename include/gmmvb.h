@@ -259,6 +259,16 @@ int hmmvb_emission_target(gmmvb_workspace* ws, int fused, int* in_effect);
  * last gmmvb_estep: z_dev[t] = state index of the most probable path (first maximiser on ties). */
 int hmmvb_viterbi(gmmvb_workspace* ws, int64_t n_rows, const double* ln_pi_tilde_dev, const double* ln_a_tilde_dev,
                   int32_t* z_dev, void* stream);
+/* The same over n_seq independent sequences laid end to end (up to 64 states; additive in ABI version 8), with the off_dev /
+ * order_dev tables of hmmvb_forward_backward_segments: every sequence's own most probable path, each started from
+ * ln_pi_tilde, in the reference's order of sums and comparisons - z_dev of a sequence's rows is bit for bit what hmmvb_viterbi's
+ * sequential form gives for those rows alone, whatever the order or the neighbours.  Every row of a non-empty sequence is
+ * written once.  Preconditions and error codes of hmmvb_viterbi; n_seq < 1: GMMVB_EINVAL; more than 64 states:
+ * GMMVB_EUNSUPPORTED.  Enqueues only; takes no host-side decision; a sequence costs its own length in serial steps;
+ * hmmvb_last_viterbi_pass reports -1 after it. */
+int hmmvb_viterbi_segments(gmmvb_workspace* ws, int64_t n_rows, int64_t n_seq, const int64_t* off_dev,
+                           const int32_t* order_dev, const double* ln_pi_tilde_dev, const double* ln_a_tilde_dev,
+                           int32_t* z_dev, void* stream);
 
 /* Row-range read-outs of the last hmmvb_forward_backward, natural state order, rows [row0, row0 + n_rows) - the
  * reference's alpha_vecs / beta_vecs [T][K] and xi_mats [T][K][K] attributes (_hiddenmarkovnormal.py:1063-1069), formed on
