@@ -126,6 +126,21 @@ def data_pass(obj, D):
     return obj._engine
 
 
+# ---- held-out scoring and many series (include/regpred.h; DESIGN.md 4f, "Held-out scoring and many series") ----------------
+def score_pass(obj, D):
+    """The model's RegressionScorePass (made on first use, kept for later calls); as ``data_pass``, no fallback."""
+    if obj._score_pass is None:
+        from ._regpred import RegressionScorePass
+        obj._score_pass = RegressionScorePass(D, obj._device)
+    return obj._score_pass
+
+
+def score_posterior(obj):
+    """(mu, L^-1, (scale, nu, c0)) of the predictive Student-t under ``hn_*``, as the scoring kernels take them."""
+    from ._regpred import student_consts
+    return obj.hn_mu_vec, inverse_factor(obj.hn_lambda_mat), student_consts(obj.hn_alpha, obj.hn_beta)
+
+
 # ---- sequential prediction (include/regseq.h; DESIGN.md 4f, "Sequential prediction") -----------------------------------------
 def seq_pass(obj, D):
     """The model's RegressionSeqPass, or the stand-in of the test seam ``obj._regseq_pass_factory``

@@ -15,6 +15,7 @@ from .. import _check, _normalgamma as ng, base
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError
 
 _D_NAME = "self.c_degree+1"
+_NO_ROW_MSG = "The length of x must greater than self.c_degree"
 
 
 class GenModel(base.Generative):
@@ -95,6 +96,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._reg_pass_factory = None        # test seam only (tests/fake_regression_engine.py)
         self._seq_engine = None
         self._regseq_pass_factory = None     # test seam only (tests/regression_seq_oracle.py)
+        self._score_pass = None
         ng.init_params(self, ("h0_", "hn_"), self.c_degree + 1)
         self.p_m = 0.0
         self.p_lambda = 0.5
@@ -115,7 +117,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def __getstate__(self):
         ng.fetch(self)
         state = dict(self.__dict__)
-        state["_engine"] = state["_seq_engine"] = None
+        state["_engine"] = state["_seq_engine"] = state["_score_pass"] = None
         return state
 
     def get_constants(self):
@@ -139,24 +141,79 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self.calc_pred_dist(np.zeros(self.c_degree))
         return self
 
-    def _check_series(self, x):
+    def _check_series(self, x, whole=True):
+        """``whole``: x is one series, which needs more than ``c_degree`` values."""
         if isinstance(x, torch.Tensor):
             if not (x.dtype.is_floating_point and x.dim() == 1):
                 raise DataFormatError("x must be a 1-dimensional numpy.ndarray.")
         else:
             _check.float_vec(x, "x", DataFormatError)
-        if x.shape[0] <= self.c_degree:
-            raise DataFormatError("The length of x must greater than self.c_degree")
+        if whole and x.shape[0] <= self.c_degree:
+            raise DataFormatError(_NO_ROW_MSG)
 
-    def update_posterior(self, x, padding=None):
-        """Conjugate update over the lag windows (ref:477-504).  As in the reference, any ``padding`` other than
-        ``"zeros"`` means none: the first ``c_degree`` values only serve as initial values."""
-        self._check_series(x)
+    def _series_tables(self, x, padding, lengths):
+        """(padding code, value offsets [S + 1], row offsets [S + 1]) of the series ``lengths`` cuts ``x`` into (None: one
+        series), host int64; everything about ``x`` and ``lengths`` is refused here, before any engine is opened."""
         from .._regression import PAD_NONE, PAD_ZEROS
-        eng = ng.data_pass(self, self.c_degree + 1)
-        stats = eng.stats_window(eng.adopt(x), PAD_ZEROS if padding == "zeros" else PAD_NONE)
+        from .._regpred import row_offsets
+        pad = PAD_ZEROS if padding == "zeros" else PAD_NONE
+        self._check_series(x, whole=lengths is None)
+        if lengths is None:
+            off = np.array([0, x.shape[0]], dtype=np.int64)
+        else:
+            from .._hmmbatch import sequence_offsets
+            off = sequence_offsets(lengths, int(x.shape[0]))
+        roff = row_offsets(off, self.c_degree, pad)
+        if roff[-1] == 0:                # no series has a row
+            raise DataFormatError(_NO_ROW_MSG)
+        return pad, off, roff
+
+    def update_posterior(self, x, padding=None, *, lengths=None):
+        """Conjugate update over the lag windows (ref:477-504).  As in the reference, any ``padding`` other than
+        ``"zeros"`` means none: the first ``c_degree`` values only serve as initial values.
+
+        ``lengths`` (1-D, non-negative integers that sum to ``len(x)``) makes ``x`` S independent series laid end to end:
+        no window reaches before the start of its own series - with ``padding == "zeros"`` every value is a row and the
+        values before a series' own start are zeros, otherwise the first ``c_degree`` values of each series are initial
+        values only and a series of at most ``c_degree`` values gives no row.  The result is what successive
+        ``update_posterior(series_s, padding)`` calls give, to rounding, from one device pass
+        (``_regpred.RegressionScorePass.stats_window``, DESIGN.md 4f "Held-out scoring and many series"); without
+        ``lengths``, or with exactly one non-empty series, it is the single-series pass, bit for bit."""
+        if lengths is None:
+            self._check_series(x)
+            from .._regression import PAD_NONE, PAD_ZEROS
+            eng = ng.data_pass(self, self.c_degree + 1)
+            stats = eng.stats_window(eng.adopt(x), PAD_ZEROS if padding == "zeros" else PAD_NONE)
+        else:
+            pad, off, roff = self._series_tables(x, padding, lengths)
+            filled = np.flatnonzero(np.diff(off))
+            if len(filled) == 1 and off[filled[0] + 1] - off[filled[0]] > self.c_degree:
+                eng = ng.data_pass(self, self.c_degree + 1)
+                stats = eng.stats_window(eng.adopt(x[int(off[filled[0]]):int(off[filled[0] + 1])]), pad)
+            else:
+                eng = ng.score_pass(self, self.c_degree + 1)
+                stats = eng.stats_window(eng.adopt(x), pad, *eng.tables(off, roff), int(roff[-1]))
         ng.update(self, stats.detach().to("cpu").numpy(), self.c_degree + 1)
         return self
+
+    def calc_pred_logpdf(self, x, padding=None, *, lengths=None, totals=False):
+        """``ln p(x[t] | its lag window)`` under the current posterior for every window row of ``update_posterior(x,
+        padding, lengths=lengths)``, in order (series after series), float64: the Student-t ``calc_pred_dist`` parametrises,
+        evaluated in one fused device pass (``_regpred.RegressionScorePass.logpdf_window``) in which the windows exist in
+        registers only.  ``x`` and ``lengths`` are accepted and refused as ``update_posterior`` does it; the return is a
+        NumPy array for NumPy input and a tensor on the model's device otherwise.  ``totals=True`` (needs ``lengths``)
+        returns ``(lnp, tot)``, ``tot`` float64 ``[S]``: each series' sum, 0.0 for a series without rows, added in a fixed
+        order on the device.  Nothing is learnt and no attribute of the model changes."""
+        if totals and lengths is None:
+            raise ParameterFormatError("totals=True returns one sum per series: pass lengths with it.")
+        pad, off, roff = self._series_tables(x, padding, lengths)
+        eng = ng.score_pass(self, self.c_degree + 1)
+        off_d, roff_d = eng.tables(off, roff)
+        lnp = eng.logpdf_window(eng.adopt(x), pad, off_d, roff_d, int(roff[-1]), *ng.score_posterior(self))
+        out = (lnp, eng.totals(lnp, roff_d)[0]) if totals else (lnp,)
+        if not isinstance(x, torch.Tensor):
+            out = tuple(v.detach().to("cpu").numpy() for v in out)
+        return out if totals else out[0]
 
     def estimate_params(self, loss="squared"):
         return ng.estimate(self, loss, 0)

@@ -98,6 +98,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         self._reg_pass_factory = None        # test seam only (tests/fake_regression_engine.py)
         self._seq_engine = None
         self._regseq_pass_factory = None     # test seam only (tests/regression_seq_oracle.py)
+        self._score_pass = None
         ng.init_params(self, ("h0_", "hn_"), self.c_degree)
         self._p = (np.zeros(1), np.ones(1))  # (p_ms, p_lambdas): ndarrays, or device tensors fetched on first read
         self.p_nus = np.full(1, 2.0)
@@ -119,7 +120,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     def __getstate__(self):
         self._fetch()
         state = dict(self.__dict__)
-        state["_engine"] = state["_seq_engine"] = None
+        state["_engine"] = state["_seq_engine"] = state["_score_pass"] = None
         return state
 
     def get_constants(self):
@@ -207,6 +208,25 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
                                     self.hn_alpha / self.hn_beta))
         self.p_nus = np.ones(x.shape[0]) * 2.0 * self.hn_alpha
         return self
+
+    def calc_pred_logpdf(self, x, y, *, total=False):
+        """``ln St(y_i | m_i, lambda_i, nu)`` of held-out rows under the current posterior, float64 ``[n]``: the density
+        ``calc_pred_dist(x)`` parametrises (ref:716-720), evaluated per row in one fused device pass
+        (``_regpred.RegressionScorePass``, DESIGN.md 4f "Held-out scoring and many series") that writes nothing but the
+        result.  ``x`` and ``y`` are accepted and refused as ``update_posterior`` does it; the return is a NumPy array for
+        NumPy input and a tensor on the model's device otherwise.  ``total=True`` returns ``(lnp, sum)``, the float64 sum
+        added in a fixed order on the device.  Nothing is learnt and no attribute of the model changes."""
+        as_numpy = not isinstance(x, torch.Tensor)
+        x, y = self._check_sample(x, y)
+        if x.shape[0] == 0:          # no rows: nothing to score, nothing to launch
+            lnp, tot = torch.zeros(0, dtype=torch.float64), 0.0
+        else:
+            eng = ng.score_pass(self, self.c_degree)
+            lnp = eng.logpdf(eng.adopt(x), eng.adopt(y), *ng.score_posterior(self))
+            tot = float(eng.totals(lnp, grand=True)[1]) if total else None
+        if as_numpy:
+            lnp = lnp.detach().to("cpu").numpy()
+        return (lnp, tot) if total else lnp
 
     def make_prediction(self, loss="squared"):
         return ng.student_t(loss, self.p_ms, self.p_lambdas, self.p_nus)
