@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .. import _check, _ctpred, _ctree, _ctseq, base
+from .. import _check, _ctfit, _ctpred, _ctree, _ctseq, base
 from . import _nodes
 from .._exceptions import CriteriaError, DataFormatError, ParameterFormatError
 
@@ -214,6 +214,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
     _ctpred_pass_factory = None       # private test seam (tests/contexttree_pred_oracle.py)
     _seq_pass = None
     _pred_pass = None
+    _fit_pass = None
     _sparse = False                   # (a model pickled before the keyword existed is dense)
 
     def __init__(self, c_k, c_d_max=2, h0_g=0.5, h0_beta_vec=None, h0_root=None, *, tables="dense", device=None):
@@ -253,6 +254,7 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
         state["_engine"] = None
         state.pop("_seq_pass", None)
         state.pop("_pred_pass", None)
+        state.pop("_fit_pass", None)
         state.pop("_store", None)           # (derived on loading: the state keeps the layout it always had)
         return state
 
@@ -351,13 +353,36 @@ class LearnModel(base.Posterior, base.PredictiveMixin):
             eng.scatter([self._store.address(0, 0)], [self.hn_g], [self.hn_beta_vec], [1], [0])
             self._has_root = True
 
-    def update_posterior(self, x):
-        """ref:712-731 in batch form; a refused sample changes nothing."""
-        xd = self._adopt_sample(x)
+    def update_posterior(self, x, *, lengths=None):
+        """ref:712-731 in batch form; a refused sample changes nothing.
+
+        ``lengths`` (1-D non-negative integers summing to ``n``) makes ``x`` the concatenation of independent sequences
+        and the call the loop ``for s in sequences: update_posterior(s)`` on this model, in one device pass
+        (``_ctfit.FitPass``, DESIGN.md "Fit from many sequences"): no context reaches before the start of its own
+        sequence, and the first ``c_d_max`` positions of every sequence end their path early.  Empty sequences are
+        allowed; with at most one non-empty sequence the call is the one without ``lengths``, bit for bit.  Dense tables
+        only."""
+        if lengths is None:
+            xd = self._adopt_sample(x)
+            seq_off = None
+        else:
+            x = self._check_sample(x)
+            seq_off = self._sequence_offsets(lengths, int(x.numel() if hasattr(x, "numel") else x.size))
+            if np.count_nonzero(np.diff(seq_off)) < 2:
+                seq_off = None
+            elif self._sparse:
+                raise NotImplementedError("update_posterior(lengths=...) with more than one non-empty sequence does not "
+                                          "support tables=\"sparse\" in this version; build the model with tables=\"dense\"")
+            xd = self._eng().adopt(x)
         eng = self._eng()
         if not self._has_root:
             eng.clear()
-        n, bad = eng.update(xd, self.hn_g, self.hn_beta_vec)
+        if seq_off is None:
+            n, bad = eng.update(xd, self.hn_g, self.hn_beta_vec)
+        else:
+            if self._fit_pass is None:
+                self._fit_pass = _ctfit.FitPass(eng)
+            n, bad = self._fit_pass.update(xd, seq_off, self.hn_g, self.hn_beta_vec)
         self._refuse_bad_symbols(xd, bad)
         self._has_root = True
         return self
